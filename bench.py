@@ -11,7 +11,15 @@ the AEAD (encrypt + decrypt) of all ranks / wall time of the K timed steps
 (max over ranks), in GiB/s (2^30 B/s).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4|5]
-                    [--no-cpu-baseline] [--no-config1] [--host-inclusive]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-config1]]
+                    [--host-inclusive]
+
+A plain run sets up, checks the round trip, warms up, times the K steps and
+prints the JSON line.  --full adds the legs that take runs of their own: the
+CPU baseline (the reference's AEAD on this host's cores) and, for config 2,
+the config-1 leg (XX loopback + 1000 x 1 KiB records, record by record).
+--dump-outputs DIR writes what the last timed step computed (ciphertext,
+decrypted plaintext, per-record status) as DIR/<name>.npy: see dump_outputs.
 
 Multi-GPU: one process per GPU.  Under torch.distributed.run (WORLD_SIZE set)
 each process is one rank.  Run directly with --gpus N > 1, this process is
@@ -472,7 +480,8 @@ def make_stub_workload(args, rank, world):
     return {"R": R, "L": L, "n_base": n_base, "workload": "stub: %d x %d B host records per rank" % (R, L),
             "step": step, "check": lambda: True, "metric": "stub", "config": {"record_bytes": L},
             "pt_bytes": R * L, "enc_bytes": R * (2 * L + 16), "dec_bytes": R * (2 * L + 17),
-            "read_bytes": (R * L, R * (L + 16)), "knames": (("stub",), ("stub",))}
+            "read_bytes": (R * L, R * (L + 16)), "knames": (("stub",), ("stub",)),
+            "outputs": {"buf": buf}}
 
 
 def make_workload(cfg, args, rank, world, stream):
@@ -585,6 +594,9 @@ def make_workload(cfg, args, rank, world, stream):
         d_ct = torch.empty(tot_ct, dtype=torch.uint8, device="cuda")
         d_back = torch.empty(tot_in, dtype=torch.uint8, device="cuda")
         d_st = torch.empty(R, dtype=torch.uint8, device="cuda")
+        if args.dump_outputs:  # no step writes the padding between records: dump it as zeros
+            d_ct.zero_()
+            d_back.zero_()
         d_key = torch.frombuffer(bytearray(KEY), dtype=torch.uint8).cuda()
         d_enc = torch.from_numpy(enc_d.view(np.uint8).copy()).cuda()
         d_dec = torch.from_numpy(dec_d.view(np.uint8).copy()).cuda()
@@ -638,6 +650,7 @@ def make_workload(cfg, args, rank, world, stream):
                             "noise_amd::k_seg_finalize_w<true", "noise_amd::k_aead_tile<true",
                             "noise_amd::k_aead_records<true")),
                 "call_level": True, "oracle": oracle,
+                "outputs": {"ct": d_ct, "back": d_back, "status": d_st},
                 "pmc_anchor": ("noise_amd::k_aead_records<false>", "noise_amd::k_aead_records<true>")}
     else:
         raise SystemExit("unknown config %d" % cfg)
@@ -647,7 +660,8 @@ def make_workload(cfg, args, rank, world, stream):
     return {"R": R, "L": L, "n_base": n_base, "workload": workload, "step": step, "check": check,
             "metric": metric, "config": cfgd, "pt_bytes": R * L,
             "enc_bytes": R * (2 * L + 16) + meta, "dec_bytes": R * (2 * L + 17) + meta,
-            "read_bytes": (R * L + meta, R * (L + 16) + meta), "knames": knames, "oracle": oracle}
+            "read_bytes": (R * L + meta, R * (L + 16) + meta), "knames": knames, "oracle": oracle,
+            "outputs": {"ct": d_ct, "back": d_back, "status": d_st}}
 
 
 def host_inclusive(R, L):
@@ -684,6 +698,50 @@ def host_inclusive(R, L):
                     "over 3 HIP streams, best of 3"}
 
 
+# ---------------------------------------------------------------- outputs
+DUMP_WHOLE = 1 << 20   # arrays up to this many bytes are written whole
+DUMP_SAMPLE = 1 << 20  # bytes sampled from a larger array
+DUMP_CHUNK = 1 << 16   # bytes per weighted sum of a larger array
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs: the byte arrays the last timed step left for its caller
+    (ciphertext||tag, decrypted plaintext, per-record status), one .npy per
+    array, byte values as float32.  An array above 1 MiB is written as two
+    files that stay small and still cover every byte: <name>_sample.npy, the
+    bytes at 2^20 fixed indices (numpy RandomState seeded with SEED, sorted),
+    and <name>_sums.npy (float64, exact), one weighted sum
+    sum_j (1 + j mod 251) * byte[j] per 64 KiB chunk (the last chunk padded
+    with zeros).  About 12 MB for the default workload, under 25 MB for any.
+    Of a multi-rank run, rank 0's shard is written."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+
+    def save(name, t, dtype):
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy().astype(dtype, copy=False))
+
+    for name, a in outputs.items():
+        if not torch.is_tensor(a):
+            a = torch.from_numpy(a)
+        a = a.reshape(-1)
+        n = a.numel()
+        if n <= DUMP_WHOLE:
+            save(name, a.to(torch.float32), np.float32)
+            continue
+        idx = np.sort(np.random.RandomState(SEED & 0xffffffff).randint(0, n, DUMP_SAMPLE, dtype=np.int64))
+        save(name + "_sample", a[torch.from_numpy(idx).to(a.device)].to(torch.float32), np.float32)
+        w = (torch.arange(DUMP_CHUNK, device=a.device, dtype=torch.int32) % 251 + 1)
+        sums = []
+        piece = 1024 * DUMP_CHUNK
+        for lo in range(0, n, piece):
+            p = a[lo:lo + piece]
+            if p.numel() % DUMP_CHUNK:
+                p = torch.cat([p, p.new_zeros(DUMP_CHUNK - p.numel() % DUMP_CHUNK)])
+            sums.append((p.view(-1, DUMP_CHUNK).to(torch.int32) * w).sum(dim=1, dtype=torch.int64))
+        save(name + "_sums", torch.cat(sums).to(torch.float64), np.float64)
+
+
 # ---------------------------------------------------------------- main
 def parse(argv):
     ap = argparse.ArgumentParser()
@@ -695,9 +753,14 @@ def parse(argv):
                          "(the GPU clock ramps over ~0.1 s; see DESIGN.md)")
     ap.add_argument("--config", type=int, default=2, choices=[1, 2, 3, 4, 5])
     ap.add_argument("--records", type=int, default=0, help="override records per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the "
+                         "CPU baseline and (config 2) the config-1 leg of the N=1 line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-config1", action="store_true",
-                    help="skip the config-1 (XX loopback + 1000 x 1 KiB) leg of the N=1 line")
+                    help="--full: skip the config-1 (XX loopback + 1000 x 1 KiB) leg of the N=1 line")
     # test hook: initialise the process group (RCCL on GPUs) even at world
     # size 1, so the barrier / reduction / gather path runs on a 1-GPU box
     ap.add_argument("--force-dist", action="store_true", help=argparse.SUPPRESS)
@@ -864,10 +927,12 @@ def main(argv=None):
             "shards": shards, "rank_spread": rank_spread(shards)}
     if args.share_device:
         line["note"] = "--share-device test run: the ranks split the visible GPU(s); not a scaling figure"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl["outputs"])
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub:
         log("cpu baseline ...")
         line["cpu_baseline"] = cpu_baseline(cfg, args.jitter)
-    if rank == 0 and world == 1 and cfg == 2 and not args.no_config1 and not args.stub:
+    if args.full and rank == 0 and world == 1 and cfg == 2 and not args.no_config1 and not args.stub:
         log("config 1 leg ...")
         line["config1"] = config1()
     if rank == 0 and args.host_inclusive and cfg == 2 and not args.stub:

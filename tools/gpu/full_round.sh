@@ -16,8 +16,7 @@ tail -3 gpurun_out/full_tests.log
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/full_smoke.log 2>&1 || { tail -20 gpurun_out/full_smoke.log; exit 1; }
 tail -1 gpurun_out/full_smoke.log
-timeout -k 10 600 python bench.py > gpurun_out/full_bench.json 2> gpurun_out/full_bench.err || { tail -20 gpurun_out/full_bench.err; exit 1; }
-cat gpurun_out/full_bench.json
+timeout -k 10 600 python bench.py --full || exit 1
 for c in ${@:-2 4}; do
   bash tools/gpu/profile_cfg.sh $c || exit 1
 done
