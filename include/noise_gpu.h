@@ -97,10 +97,17 @@ int noise_gpu_device_count(int *count);
  * 1536, 1792, 2304, 2560, 3072, 5120); unaligned records (strides or bases
  * not multiples of 16) of len <= 16384 without AD, in batches of >= 1024
  * records that do not partially overlap, are copied into an aligned image in
- * the library's scratch for (device, stream) (noise_gpu_scratch_wipe clears
- * it), processed there and copied back; other shapes (AD, len > 16384, small
- * unaligned batches) one record per lane (vector path when 16-byte aligned
- * with len % 16 == 0, byte-granular otherwise).
+ * the library's scratch for (device, stream), processed there and copied
+ * back; other shapes (AD, len > 16384, small unaligned batches) one record
+ * per lane (vector path when 16-byte aligned with len % 16 == 0,
+ * byte-granular otherwise).
+ * Hygiene: such an unaligned batch LEAVES AN IMAGE OF EVERY RECORD, plaintext
+ * and ciphertext, in that scratch after the call.  These functions do not
+ * wipe it (that would cost the device-resident path a pass over memory): the
+ * caller does, with noise_gpu_scratch_wipe(stream) after the last such call
+ * and noise_gpu_scratch_release(stream) before destroying the stream.  The
+ * host-buffer entry points (*_host, noise_gpu_ctx_*) wipe it themselves
+ * before they return.
  * Key handling: h_key is copied into the kernel's argument block (kernarg
  * memory) by value, so the 32-byte key stays in that launch's kernarg
  * segment after the call, like any kernel argument; the runtime reuses,
@@ -178,19 +185,25 @@ int noise_gpu_decrypt_records_sized(const uint8_t *d_keys, uint32_t nkeys,
                                     const uint8_t *d_in, uint8_t *d_out, const uint8_t *d_ad,
                                     uint8_t *d_status, uint64_t len_sum, void *stream);
 
-/* The descriptor path keeps a grow-only device scratch per (device,
- * stream) that holds, between the kernels of a call, copies of the long
- * records' keys, their one-time Poly1305 keys and partial sums.  This zeroes
- * it (stream-ordered after the calls already issued on `stream`), e.g. at
- * session teardown.  The host-buffer entry points below wipe it themselves. */
+/* The library keeps one grow-only device scratch per (device, stream),
+ * shared by the two paths that need one.  The descriptor path holds in it,
+ * between the kernels of a call, copies of the long records' keys, their
+ * one-time Poly1305 keys and partial sums; noise_gpu_{en,de}crypt_uniform
+ * stage an unaligned batch through it, which leaves an image of every record
+ * (plaintext and ciphertext) there.  This zeroes it (stream-ordered after the
+ * calls already issued on `stream`), e.g. at session teardown.  The
+ * host-buffer entry points below (*_host, noise_gpu_ctx_*) wipe it
+ * themselves. */
 int noise_gpu_scratch_wipe(void *stream);
 
-/* Zero and free the records scratch and the companion stream the descriptor
- * path cached for (current device, `stream`); synchronises `stream` first.
+/* Zero and free that scratch and the companion streams the descriptor path
+ * cached for (current device, `stream`); synchronises `stream` first.
  * Call it before destroying a stream of your own that the descriptor
- * functions were called on (noise_gpu_ctx_destroy does it for the context's
- * streams); otherwise both stay allocated until the library is unloaded.
- * A stream with nothing cached is a no-op. */
+ * functions, or the uniform functions with an unaligned batch, were called on;
+ * otherwise both stay allocated until the library is unloaded.  The streams
+ * the library itself creates for the host-buffer entry points are released
+ * this way whenever they are destroyed (thread exit, noise_gpu_thread_release,
+ * noise_gpu_ctx_destroy).  A stream with nothing cached is a no-op. */
 int noise_gpu_scratch_release(void *stream);
 
 /* ---- device-resident many-session batches (BASELINE config 3) ---------
@@ -429,7 +442,8 @@ int noise_gpu_decrypt_records_host(const uint8_t *h_keys, uint32_t nkeys,
  * Streams, events and device buffers live in a context per (calling thread,
  * current device) that persists across calls (created on the thread's first
  * call on that device; a thread serving several GPUs keeps one per device);
- * their contents are zeroed at the end of every call.  The single-record
+ * their contents are zeroed at the end of every call, the staging scratch of
+ * an unaligned batch (packed records with len % 16 != 0) included.  The single-record
  * and descriptor host entry points above keep their staging the same way.
  * Footprint of that per-(thread, device) state: the uniform pipeline holds
  * 3 x 34 MiB of device memory and 3 streams; the descriptor path a device
@@ -453,16 +467,16 @@ int noise_gpu_decrypt_uniform_host(const uint8_t h_key[32], uint64_t nonce0,
                                    uint64_t nrec, double *seconds);
 
 /* Wipe and free every per-(calling thread, device) context the host-buffer
- * entry points created for this thread (staging, records scratch and its
- * companion stream, the latency-path buffer, the uniform pipeline), on all
- * devices.  The next call re-creates what it needs.  Synchronises the
+ * entry points created for this thread (staging, the latency-path buffer,
+ * the uniform pipeline, and the scratch and companion streams cached for
+ * their streams), on all devices.  The next call re-creates what it needs.  Synchronises the
  * thread's streams. */
 int noise_gpu_thread_release(void);
 
 /* ---- explicit device contexts --------------------------------------------
  * SURVEY 8(b) proposed noise_gpu_ctx_create(int device, ...).  The device-
  * resident entry points above need no context (a stream names the device's
- * work; the records scratch is kept per (device, stream)).  The host-buffer
+ * work; the library's scratch is kept per (device, stream)).  The host-buffer
  * entry points otherwise keep their staging per (calling thread, current
  * device); a noise_gpu_ctx instead owns that state for one device, so a
  * server can bind one context per GPU (or per connection thread) without
@@ -471,7 +485,7 @@ int noise_gpu_thread_release(void);
  * device afterwards; it behaves exactly like the context-free function of
  * the same name.  A context is not thread-safe: one thread at a time (like
  * a CipherState).  destroy wipes and frees everything the context staged,
- * including the descriptor path's records scratch and companion stream. */
+ * including the scratch and companion streams cached for its streams. */
 typedef struct noise_gpu_ctx noise_gpu_ctx;
 /* device: HIP device index (must be gfx950, else NOISE_GPU_E_NODEV) */
 int noise_gpu_ctx_create(int device, noise_gpu_ctx **out);

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "noise_gpu.h"
+#include "stream_res.hpp"  // per-stream scratch and companions (records_scratch_*)
 
 namespace noise_amd {
 
@@ -24,15 +25,6 @@ hipError_t launch_aead_records(bool decrypt, const uint8_t *keys,
                                uint64_t nrec, const uint8_t *in, uint8_t *out,
                                const uint8_t *ad, uint8_t *status,
                                hipStream_t stream, uint64_t len_sum = 0);
-
-// zero the records-path scratch of (current device, stream)
-hipError_t records_scratch_wipe(hipStream_t stream);
-// the grow-only scratch of (current device, stream), >= bytes; the records
-// path and the uniform path's staging of unaligned batches share it
-hipError_t records_scratch_get(void **p, size_t bytes, hipStream_t stream);
-// zero + free the scratch and destroy the companion stream cached for
-// (current device, stream); call before destroying `stream`
-hipError_t records_scratch_release(hipStream_t stream);
 
 bool sessions_supported(uint32_t len, const void *in, uint64_t in_stride,
                         const void *out, uint64_t out_stride);

@@ -98,31 +98,47 @@ int check_uniform(bool decrypt, const void *in, uint64_t in_stride,
   return NOISE_GPU_OK;
 }
 
+// A stream the engine created (non-blocking, on the device current at open).
+// Closing it first releases what the launchers cached under it -- scratch and
+// companion streams (stream_res.hpp), which synchronises it -- so neither
+// outlives the stream.  Launches take the raw handle.  close() runs on the
+// stream's device: the owning context holds a DeviceGuard around it.
+struct OwnedStream {
+  hipStream_t s = nullptr;
+  OwnedStream() = default;
+  OwnedStream(OwnedStream &&o) noexcept : s(o.s) { o.s = nullptr; }  // move-only; no assignment
+  ~OwnedStream() { close(); }
+  hipError_t open() {
+    close();
+    return hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+  }
+  void close() {
+    if (!s) return;
+    (void)noise_amd::records_scratch_release(s);
+    (void)hipStreamDestroy(s);
+    s = nullptr;
+  }
+  operator hipStream_t() const { return s; }
+};
+
 // Per-thread staging for the synchronous host-buffer entry points.
 struct Staging {
   int dev = -1;
-  hipStream_t stream = nullptr;
+  OwnedStream stream;
   uint8_t *d = nullptr, *h = nullptr;
   size_t cap = 0;
   ~Staging() { release(); }
-  // free everything, including the records scratch and companion stream the
-  // descriptor path cached for this staging stream (records_scratch_release)
   void release() {
-    int cur = -1;
-    if (stream && dev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != dev) (void)hipSetDevice(dev);
-    if (stream) (void)noise_amd::records_scratch_release(stream);
-    if (d) {  // wiped and freed stream-ordered (dev_mem.hpp), then waited for
-      (void)noise_amd::dev_wipe_free(d, cap, stream);
-      (void)hipStreamSynchronize(stream);
-    }
+    if (dev < 0) return;
+    noise_amd::DeviceGuard on(dev);
+    // wiped and freed stream-ordered (dev_mem.hpp); the close waits for it
+    if (d) (void)noise_amd::dev_wipe_free(d, cap, stream);
+    stream.close();
     if (h) {
       std::memset(h, 0, cap);
       (void)hipHostFree(h);
     }
-    if (stream) (void)hipStreamDestroy(stream);
-    if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
     d = h = nullptr;
-    stream = nullptr;
     cap = 0;
     dev = -1;
   }
@@ -136,10 +152,10 @@ struct Staging {
   int reserve(size_t bytes) {
     int cur = 0;
     HIP_TRY(hipGetDevice(&cur));
-    if (cur != dev) {  // device switched: drop the old device's resources
+    if (cur != dev || !stream) {  // device switched: drop the old device's resources
       release();
       dev = cur;
-      HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+      HIP_TRY(stream.open());
     }
     if (bytes <= cap) return NOISE_GPU_OK;
     size_t want = cap ? cap : 4096;
@@ -231,6 +247,8 @@ static int req_kind_env() {
 
 struct OneCtx {
   int dev = -1;
+  // raw streams: the latency launchers take no scratch, and rstream must
+  // never be synchronised once `wedged` is set (an OwnedStream's close would)
   hipStream_t stream = nullptr;
   uint8_t *h = nullptr;  // host view
   uint8_t *d = nullptr;  // device view of the same memory
@@ -320,14 +338,11 @@ struct OneCtx {
     return NOISE_GPU_OK;
   }
   void release() {
-    int cur = -1;
-    if (stream && dev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != dev) (void)hipSetDevice(dev);
-    if (stop_resident() != NOISE_GPU_OK) {
-      // a wedged instance still runs from this context's memory: leave it all
-      // allocated (leaked) rather than free it under the kernel or hang here
-      if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
-      return;
-    }
+    if (dev < 0) return;
+    noise_amd::DeviceGuard on(dev);
+    // a wedged instance still runs from this context's memory: leave it all
+    // allocated (leaked) rather than free it under the kernel or hang here
+    if (stop_resident() != NOISE_GPU_OK) return;
     if (stream) (void)hipStreamSynchronize(stream);
     release_req();
     if (rstream) {
@@ -340,7 +355,6 @@ struct OneCtx {
       (void)hipHostFree(h);
     }
     if (stream) (void)hipStreamDestroy(stream);
-    if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
     h = d = nullptr;
     stream = nullptr;
     cap = 0;
@@ -993,16 +1007,18 @@ struct PipeCtx {
   static constexpr int kDepth = 3;
   static constexpr uint64_t kChunk = 32ull << 20;  // bytes in + out per chunk
   int dev = -1;
-  hipStream_t st[kDepth] = {};
+  OwnedStream st[kDepth];
   uint8_t *buf[kDepth] = {};  // [in | out | status] of one chunk
   ~PipeCtx() { release(); }
+  // the chunks wiped and freed stream-ordered; each stream's close waits for
+  // that and releases the staging scratch of unaligned batches with it
   void release() {
+    if (dev < 0) return;
+    noise_amd::DeviceGuard on(dev);
     for (int i = 0; i < kDepth; ++i) {
       if (buf[i]) (void)noise_amd::dev_wipe_free(buf[i], kChunk + (kChunk >> 4), st[i]);
-      if (st[i]) (void)hipStreamSynchronize(st[i]);
-      if (st[i]) (void)hipStreamDestroy(st[i]);
+      st[i].close();
       buf[i] = nullptr;
-      st[i] = nullptr;
     }
     dev = -1;
   }
@@ -1011,11 +1027,16 @@ struct PipeCtx {
     HIP_TRY(hipGetDevice(&cur));
     if (cur == dev) return NOISE_GPU_OK;
     release();
+    dev = cur;  // from here on release() has something to drop, on this device
     for (int i = 0; i < kDepth; ++i) {
-      HIP_TRY(hipStreamCreateWithFlags(&st[i], hipStreamNonBlocking));
-      HIP_TRY(noise_amd::dev_alloc(reinterpret_cast<void **>(&buf[i]), kChunk + (kChunk >> 4), st[i]));
+      hipError_t e = st[i].open();
+      if (e == hipSuccess)
+        e = noise_amd::dev_alloc(reinterpret_cast<void **>(&buf[i]), kChunk + (kChunk >> 4), st[i]);
+      if (e != hipSuccess) {
+        release();
+        return hip_fail(e, "host pipeline setup");
+      }
     }
-    dev = cur;
     return NOISE_GPU_OK;
   }
 };
@@ -1078,9 +1099,13 @@ static int uniform_host(bool decrypt, const uint8_t h_key[32], uint64_t nonce0,
   std::memset(k, 0, sizeof k);
   for (int i = 0; i < PipeCtx::kDepth && e == hipSuccess; ++i) e = hipStreamSynchronize(P.st[i]);
   const auto t1 = std::chrono::steady_clock::now();
-  // hygiene: the chunks held plaintext and ciphertext
+  // hygiene: the chunks held plaintext and ciphertext, and so did the staging
+  // scratch of an unaligned batch (nothing to do for a stream that took none)
   for (int i = 0; i < PipeCtx::kDepth; ++i)
-    if (used[i]) (void)hipMemsetAsync(P.buf[i], 0, used[i], P.st[i]);
+    if (used[i]) {
+      (void)hipMemsetAsync(P.buf[i], 0, used[i], P.st[i]);
+      (void)noise_amd::records_scratch_wipe(P.st[i]);
+    }
   if (e != hipSuccess) {
     P.release();
     return hip_fail(e, "host pipeline");
@@ -1124,16 +1149,14 @@ struct noise_gpu_ctx {
 
 namespace {
 struct CtxScope {
-  int prev = -1;
+  noise_amd::DeviceGuard on;  // first member: the device is restored last
   Staging *s0;
   OneCtx *o0;
   PipeCtx *p0;
   int rc = NOISE_GPU_OK;
-  explicit CtxScope(noise_gpu_ctx *c) : s0(tl_stage), o0(tl_one), p0(tl_pipe) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    const hipError_t e = hipSetDevice(c->device);
-    if (e != hipSuccess) {
-      rc = hip_fail(e, "hipSetDevice(ctx device)");
+  explicit CtxScope(noise_gpu_ctx *c) : on(c->device), s0(tl_stage), o0(tl_one), p0(tl_pipe) {
+    if (on.err != hipSuccess) {
+      rc = hip_fail(on.err, "hipSetDevice(ctx device)");
       return;
     }
     tl_stage = &c->stage;
@@ -1144,7 +1167,6 @@ struct CtxScope {
     tl_stage = s0;
     tl_one = o0;
     tl_pipe = p0;
-    if (prev >= 0) (void)hipSetDevice(prev);
   }
 };
 }  // namespace
@@ -1183,14 +1205,11 @@ int noise_gpu_set_resident(int on, uint32_t idle_us) {
 }
 
 int noise_gpu_thread_release(void) {
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-  for (int i = 0; i < kMaxCtxDev; ++i) {
+  for (int i = 0; i < kMaxCtxDev; ++i) {  // each on its own device (DeviceGuard)
     g_stage_tab[i].release();
     g_one_tab[i].release();
     g_pipe_tab[i].release();
   }
-  if (prev >= 0) (void)hipSetDevice(prev);
   return NOISE_GPU_OK;
 }
 
@@ -1203,12 +1222,11 @@ int noise_gpu_ctx_create(int device, noise_gpu_ctx **out) {
     return NOISE_GPU_E_NODEV;
   }
   if (device < 0 || device >= n) return arg_fail("device index out of range");
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-  HIP_TRY(hipSetDevice(device));
-  const int rc = check_device();  // gfx950 only
-  if (prev >= 0) (void)hipSetDevice(prev);
-  if (rc) return rc;
+  {
+    noise_amd::DeviceGuard on(device);
+    if (on.err != hipSuccess) return hip_fail(on.err, "hipSetDevice(device)");
+    if (int rc = check_device()) return rc;  // gfx950 only
+  }
   noise_gpu_ctx *c = new (std::nothrow) noise_gpu_ctx;
   if (!c) return arg_fail("out of host memory");
   c->device = device;
@@ -1218,11 +1236,8 @@ int noise_gpu_ctx_create(int device, noise_gpu_ctx **out) {
 
 int noise_gpu_ctx_destroy(noise_gpu_ctx *ctx) {
   if (!ctx) return NOISE_GPU_OK;
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-  (void)hipSetDevice(ctx->device);
+  noise_amd::DeviceGuard on(ctx->device);
   delete ctx;  // the contexts wipe what they staged, then free it
-  if (prev >= 0) (void)hipSetDevice(prev);
   return NOISE_GPU_OK;
 }
 

@@ -31,14 +31,11 @@
 //          -> one lane per record (chachapoly_device.hpp).
 // Small batches (< kClassifyMin records) skip all this and run the generic
 // kernel directly (latency of single records from CipherState).
-// Scratch is a grow-only device buffer cached per (device, stream).
-#include <mutex>
-#include <vector>
-
+// Scratch and the companion streams are cached per (device, stream)
+// (stream_res.hpp).
 #include "chachapoly_device.hpp"
 #include "launchers.hpp"
 #include "mtile_kernel.hpp"
-#include "noise_amd/dev_mem.hpp"
 #include "tile_kernel.hpp"
 
 namespace noise_amd {
@@ -65,11 +62,8 @@ constexpr int kCols = kNumCls + 2 + kFinBuckets;
 // the Poly1305 pass of chunk c + 1 (HBM-bound) runs beside the keystream pass
 // of chunk c (VALU-bound).  Chunk boundaries fall on record starts, near
 // (1 + (c - 1) W) nseg / (1 + (kSegChunks - 1) W) segments (chunk 0 1/W of
-// the others, W = kChunkW).
-#ifndef NOISE_SEG_CHUNKS
-#define NOISE_SEG_CHUNKS 4
-#endif
-constexpr int kSegChunks = NOISE_SEG_CHUNKS;
+// the others, W = kChunkW).  kSegChunks (NOISE_SEG_CHUNKS) is in
+// stream_res.hpp: the companion set holds two events per chunk.
 #ifndef NOISE_CHUNK_W
 #define NOISE_CHUNK_W 4
 #endif
@@ -709,210 +703,10 @@ __global__ __launch_bounds__(kGenBlock) void k_aead_records(
   }
 }
 
-// ---- scratch: one grow-only buffer per (device, stream) ------------------
-// Calls on one stream are ordered, so they may share the buffer.  It only
-// grows; the smaller one is wiped and freed stream-ordered (dev_mem.hpp), so
-// it is released after the launches that still use it, and the grow waits for
-// nothing else on the device (hipFree would wait for every stream, e.g. for a
-// resident latency instance serving another thread).
-struct ScratchEntry {
-  int dev;
-  hipStream_t stream;
-  void *ptr;
-  size_t size;
-};
-static std::mutex g_scratch_mu;
-static std::vector<ScratchEntry> g_scratch;
-
-static void scratch_find(int dev, hipStream_t stream, void **p, size_t *size) {
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  for (const ScratchEntry &en : g_scratch)
-    if (en.dev == dev && en.stream == stream) {
-      *p = en.ptr;
-      *size = en.size;
-      return;
-    }
-}
-
-static hipError_t scratch_get(void **p, size_t bytes, hipStream_t stream) {
-  using Entry = ScratchEntry;
-  auto &mu = g_scratch_mu;
-  auto &cache = g_scratch;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  std::lock_guard<std::mutex> lk(mu);
-  for (Entry &en : cache) {
-    if (en.dev != dev || en.stream != stream) continue;
-    if (en.size < bytes) {
-      if ((e = dev_wipe_free(en.ptr, en.size, stream)) != hipSuccess) return e;
-      en.ptr = nullptr;
-      en.size = 0;
-      if ((e = dev_alloc(&en.ptr, bytes, stream)) != hipSuccess) return e;
-      en.size = bytes;
-    }
-    *p = en.ptr;
-    return hipSuccess;
-  }
-  void *ptr = nullptr;
-  if ((e = dev_alloc(&ptr, bytes, stream)) != hipSuccess) return e;
-  cache.push_back({dev, stream, ptr, bytes});
-  *p = ptr;
-  return hipSuccess;
-}
-
-hipError_t records_scratch_get(void **p, size_t bytes, hipStream_t stream) {
-  return scratch_get(p, bytes, stream);
-}
-
-// Zero the scratch of (current device, stream): the long-record table holds
-// key copies, one-time Poly1305 keys and partial sums between the kernels of
-// a call.  Stream-ordered after the call's kernels.
-hipError_t records_scratch_wipe(hipStream_t stream) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  void *ptr = nullptr;
-  size_t size = 0;
-  scratch_find(dev, stream, &ptr, &size);
-  if (!ptr) return hipSuccess;
-  return hipMemsetAsync(ptr, 0, size, stream);
-}
-
-// Release everything cached for (current device, stream): the scratch is
-// zeroed and freed, the companion stream and its events destroyed.  Called
-// before a stream the engine owns is destroyed (noise_gpu_ctx_destroy,
-// per-thread staging teardown), so neither a dead stream's scratch nor its
-// companion outlives it.  Synchronises `stream` first.
-static hipError_t aux_release(int dev, hipStream_t stream);
-hipError_t records_scratch_release(hipStream_t stream) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  void *ptr = nullptr;
-  size_t size = 0;
-  {
-    std::lock_guard<std::mutex> lk(g_scratch_mu);
-    for (size_t i = 0; i < g_scratch.size(); ++i)
-      if (g_scratch[i].dev == dev && g_scratch[i].stream == stream) {
-        ptr = g_scratch[i].ptr;
-        size = g_scratch[i].size;
-        g_scratch.erase(g_scratch.begin() + (std::ptrdiff_t)i);
-        break;
-      }
-  }
-  if (ptr) e = dev_wipe_free(ptr, size, stream);  // after the calls queued on `stream`
-  const hipError_t e2 = hipStreamSynchronize(stream);
-  if (e == hipSuccess) e = e2;
-  const hipError_t e3 = aux_release(dev, stream);
-  return e == hipSuccess ? e3 : e;
-}
-
 static inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 static inline unsigned capped(uint64_t want, uint64_t cap) {
   if (want == 0) want = 1;
   return (unsigned)(want < cap ? want : cap);
-}
-
-// Fork/join companion of a caller stream: a non-blocking stream and two
-// events, cached per (device, stream) like the scratch.  The records DAG has
-// two independent branches after the classifier (below); the short ones run
-// on the companion stream while the segment kernel fills the GPU.
-struct AuxStream {
-  hipStream_t aux = nullptr;   // companion: small classes, generic, tails
-  hipStream_t aux2 = nullptr;  // decrypt: per chunk, tag check + plaintext pass
-  hipStream_t aux3 = nullptr;  // the whole-record classes of 2 .. 16 KiB
-  // fork: classifier done; prep: k_seg_prep done; join: encrypt: the
-  // companion branch done, decrypt: the tails' Poly1305 done; join2: the
-  // companion done (decrypt); xdone: the last plaintext pass done; poly[c] /
-  // fin[c]: chunk c's Poly1305 pass / tag check done
-  hipEvent_t fork = nullptr, prep = nullptr, join = nullptr, join2 = nullptr, xdone = nullptr,
-             big = nullptr;  // big: the whole-record classes done
-  hipEvent_t poly[kSegChunks] = {}, fin[kSegChunks] = {};
-};
-struct AuxEntry {
-  int dev;
-  hipStream_t stream;
-  AuxStream a;
-};
-static std::mutex g_aux_mu;
-static std::vector<AuxEntry> g_aux;
-
-static hipError_t aux_get(AuxStream *out, hipStream_t stream) {
-  auto &mu = g_aux_mu;
-  auto &cache = g_aux;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  std::lock_guard<std::mutex> lk(mu);
-  for (const AuxEntry &en : cache)
-    if (en.dev == dev && en.stream == stream) {
-      *out = en.a;
-      return hipSuccess;
-    }
-  AuxStream a;
-  // on any failure, what was created so far is destroyed again
-  auto undo = [&a]() {
-    for (hipStream_t st : {a.aux, a.aux2, a.aux3})
-      if (st) (void)hipStreamDestroy(st);
-    for (hipEvent_t ev : {a.fork, a.prep, a.join, a.join2, a.xdone, a.big})
-      if (ev) (void)hipEventDestroy(ev);
-    for (int c = 0; c < kSegChunks; ++c)
-      for (hipEvent_t ev : {a.poly[c], a.fin[c]})
-        if (ev) (void)hipEventDestroy(ev);
-  };
-  for (hipStream_t *st : {&a.aux, &a.aux2, &a.aux3})
-    if ((e = hipStreamCreateWithFlags(st, hipStreamNonBlocking)) != hipSuccess) {
-      undo();
-      return e;
-    }
-  for (hipEvent_t *ev : {&a.fork, &a.join, &a.prep, &a.join2, &a.xdone, &a.big})
-    if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) {
-      undo();
-      return e;
-    }
-  for (int c = 0; c < kSegChunks; ++c)
-    for (hipEvent_t *ev : {&a.poly[c], &a.fin[c]})
-      if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) {
-        undo();
-        return e;
-      }
-  cache.push_back({dev, stream, a});
-  *out = a;
-  return hipSuccess;
-}
-
-static hipError_t aux_release(int dev, hipStream_t stream) {
-  AuxStream a;
-  bool found = false;
-  {
-    std::lock_guard<std::mutex> lk(g_aux_mu);
-    for (size_t i = 0; i < g_aux.size(); ++i)
-      if (g_aux[i].dev == dev && g_aux[i].stream == stream) {
-        a = g_aux[i].a;
-        g_aux.erase(g_aux.begin() + (std::ptrdiff_t)i);
-        found = true;
-        break;
-      }
-  }
-  if (!found) return hipSuccess;
-  hipError_t e = hipSuccess, e2;
-  for (hipStream_t st : {a.aux, a.aux2, a.aux3}) {
-    e2 = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = e2;
-    e2 = hipStreamDestroy(st);
-    if (e == hipSuccess) e = e2;
-  }
-  for (hipEvent_t ev : {a.fork, a.prep, a.join, a.join2, a.xdone, a.big}) {
-    e2 = hipEventDestroy(ev);
-    if (e == hipSuccess) e = e2;
-  }
-  for (int c = 0; c < kSegChunks; ++c)
-    for (hipEvent_t ev : {a.poly[c], a.fin[c]}) {
-      e2 = hipEventDestroy(ev);
-      if (e == hipSuccess) e = e2;
-    }
-  return e;
 }
 
 // After the classifier, two branches.  Encrypt:
@@ -950,7 +744,7 @@ static hipError_t launch_classes(const TileArgs &ta, uint64_t nrec, const RecHdr
                                  uint8_t *out, const uint8_t *ad, uint8_t *status,
                                  hipStream_t stream, int chunks) {
   AuxStream ax;
-  hipError_t e = aux_get(&ax, stream);
+  hipError_t e = records_aux_get(&ax, stream);
   if (e != hipSuccess) return e;
   const dim3 bt(64);
   const dim3 grid(capped((nrec + 63) / 64, NOISE_GRID_CAP));
@@ -1122,7 +916,7 @@ hipError_t launch_aead_records(bool decrypt, const uint8_t *keys,
   const uint64_t o_phi = align_up(o_part2 + segcap * sizeof(SegPartial), 256);
   const uint64_t bytes = o_phi + segcap * sizeof(uint32_t);
   void *mem = nullptr;
-  hipError_t e = scratch_get(&mem, bytes, stream);
+  hipError_t e = records_scratch_get(&mem, bytes, stream);
   if (e != hipSuccess) return e;
   uint8_t *base = static_cast<uint8_t *>(mem);
   RecHdr *hdr = reinterpret_cast<RecHdr *>(base);

@@ -4,7 +4,7 @@
 // hipFree (and hipHostFree) on ROCm wait for every stream of the device before
 // they return.  A resident latency instance (noise_gpu_set_resident) occupies
 // its stream until it idles out, so with steady single-record traffic on one
-// thread, a hipFree on another thread -- a records scratch that grows, a
+// thread, a hipFree on another thread -- a stream's scratch that grows, a
 // Pipeline key table that doubles -- would wait for a gap in that traffic,
 // possibly for ever.  hipMallocAsync / hipFreeAsync order the allocation and
 // the free on ONE stream instead: the free happens once the work queued on that
@@ -73,9 +73,10 @@ inline hipError_t dev_wipe_free(void *p, size_t bytes, hipStream_t stream) {
 // target the owner's device whatever device the calling thread has current
 struct DeviceGuard {
   int prev = -1, want;
+  hipError_t err = hipSuccess;  // of the switch to `dev`, for owners that report it
   explicit DeviceGuard(int dev) : want(dev) {
     if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != want) (void)hipSetDevice(want);
+    if (prev != want) err = hipSetDevice(want);
   }
   ~DeviceGuard() {
     if (prev >= 0 && prev != want) (void)hipSetDevice(prev);

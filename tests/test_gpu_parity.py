@@ -351,10 +351,14 @@ def test_config2_full_size_round_trip(oracle):
         assert d_pt[i * L:(i + 1) * L].cpu().numpy().tobytes() == oracle.synthetic(L, SEED, i * L)
 
 
-def test_host_pipeline_matches_device(oracle):
-    """Transfer-inclusive host API == device kernels (pinned buffers)."""
+@pytest.mark.parametrize("L,R", [(1024, 3000), (1000, 1100)])
+def test_host_pipeline_matches_device(oracle, L, R):
+    """Transfer-inclusive host API == device kernels (pinned buffers), packed
+    strides.  1000-byte records are unaligned on the device chunk, so the
+    pipeline's stream stages them through its scratch (>= 1024 records).
+    Every record of both directions against the oracle, the round trip, and
+    one tampered record per third of the batch: REC_BAD_MAC, output row zero."""
     rng = random.Random(4)
-    R, L = 3000, 1024
     key = rng.randbytes(32)
     pt = torch.from_numpy(np.frombuffer(rng.randbytes(R * L), dtype=np.uint8).copy()).pin_memory()
     ct = torch.zeros(R * (L + 16), dtype=torch.uint8).pin_memory()
@@ -371,10 +375,28 @@ def test_host_pipeline_matches_device(oracle):
                                               ctypes.c_void_p(st.data_ptr()), R,
                                               ctypes.byref(secs)) == 0
     assert torch.equal(pt, back) and int(st.sum()) == 0
+    assert oracle.check_uniform(False, key, 10, pt.numpy(), L, ct.numpy(), L + 16, L, R) == (0, -1)
+    assert oracle.check_uniform(True, key, 10, ct.numpy(), L + 16, back.numpy(), L, L, R,
+                                status=st.numpy()) == (0, -1)
     c = ct.numpy().tobytes()
-    for i in (0, 1, 1234, R - 1):
+    for i in (0, 1, R // 2 - 266, R - 1):
         assert c[i * (L + 16):(i + 1) * (L + 16)] == oracle.encrypt(
             key, 10 + i, b"", pt[i * L:(i + 1) * L].numpy().tobytes())
+    # one tampered record per third of the batch
+    bad = (R // 6, R // 2 + 1, R - 1)
+    for i in bad:
+        ct[i * (L + 16) + rng.randrange(L + 16)] ^= 0x40
+    back.fill_(0xAA)
+    st.fill_(9)
+    assert lib.noise_gpu_decrypt_uniform_host(key, 10, ctypes.c_void_p(ct.data_ptr()), L + 16,
+                                              ctypes.c_void_p(back.data_ptr()), L, L,
+                                              ctypes.c_void_p(st.data_ptr()), R,
+                                              ctypes.byref(secs)) == 0
+    rows, want = back.view(R, L), pt.view(R, L)
+    for i in bad:
+        assert int(st[i]) == noise_amd.REC_BAD_MAC and not rows[i].any(), i
+        want[i].zero_()
+    assert int(st.sum()) == len(bad) * noise_amd.REC_BAD_MAC and torch.equal(rows, want)
 
 
 def test_device_context_api(oracle, golden):
@@ -411,19 +433,28 @@ def test_device_context_api(oracle, golden):
         for i, r in enumerate(recs):
             o = int(dsc[i]["out_off"])
             assert out.raw[o:o + len(r["pt"]) + 16] == r["ct"]
-        R, L = 500, 1024
-        pt = rng.randbytes(R * L)
-        ct = ctypes.create_string_buffer(R * (L + 16))
-        back = ctypes.create_string_buffer(R * L)
-        st = ctypes.create_string_buffer(b"\x09" * R, R)
-        secs = ctypes.c_double()
-        assert lib.noise_gpu_ctx_encrypt_uniform_host(h, key, 9, pt, L, ct, L + 16, L, R,
-                                                      ctypes.byref(secs)) == 0
-        assert lib.noise_gpu_ctx_decrypt_uniform_host(h, key, 9, ct, L + 16, back, L, L, st, R,
-                                                      ctypes.byref(secs)) == 0
-        assert back.raw == pt and st.raw == bytes(R)
-        assert ct.raw[(R - 1) * (L + 16):] == oracle.encrypt(key, 9 + R - 1, b"", pt[(R - 1) * L:])
+        def uniform_host(h, R, L):
+            pt = rng.randbytes(R * L)
+            ct = ctypes.create_string_buffer(R * (L + 16))
+            back = ctypes.create_string_buffer(R * L)
+            st = ctypes.create_string_buffer(b"\x09" * R, R)
+            secs = ctypes.c_double()
+            assert lib.noise_gpu_ctx_encrypt_uniform_host(h, key, 9, pt, L, ct, L + 16, L, R,
+                                                          ctypes.byref(secs)) == 0
+            assert lib.noise_gpu_ctx_decrypt_uniform_host(h, key, 9, ct, L + 16, back, L, L, st, R,
+                                                          ctypes.byref(secs)) == 0
+            assert back.raw == pt and st.raw == bytes(R)
+            assert ct.raw[(R - 1) * (L + 16):] == oracle.encrypt(key, 9 + R - 1, b"", pt[(R - 1) * L:])
+        uniform_host(h, 500, 1024)
+        uniform_host(h, 1100, 1000)  # unaligned: staged through the pipeline stream's scratch
         assert torch.cuda.current_device() == 0
+    finally:
+        assert lib.noise_gpu_ctx_destroy(h) == 0
+    # destroy released the streams with what was cached under them: a second
+    # context on the same device starts from nothing and works
+    assert lib.noise_gpu_ctx_create(0, ctypes.byref(h)) == 0 and h.value
+    try:
+        uniform_host(h, 1100, 1000)
     finally:
         assert lib.noise_gpu_ctx_destroy(h) == 0
 

@@ -158,6 +158,40 @@ static void refused_request(const char *what, double limit_s, const uint8_t key[
   scan("after the refused request", true);
 }
 
+// The unaligned host-pipeline shape: 1100 packed records of 1000 bytes, so
+// the pipeline's stream takes staging scratch (two slices: 1024 + 76
+// records).  Encrypt and decrypt against the oracle on every record, every
+// allocation zero after each call.  ctx == nullptr: the calling thread's own
+// contexts.
+static void unaligned_uniform(noise_gpu_ctx *ctx, const uint8_t key[32], uint64_t seed,
+                              const char *what, bool resident) {
+  const uint32_t L = 1000, R = 1100;
+  std::mt19937_64 rng(seed);
+  std::vector<uint8_t> pt((size_t)L * R), ct((size_t)(L + 16) * R), back((size_t)L * R), st(R, 9);
+  for (auto &x : pt) x = (uint8_t)rng();
+  double secs = 0;
+  ++calls;
+  int rc = ctx ? noise_gpu_ctx_encrypt_uniform_host(ctx, key, 11, pt.data(), L, ct.data(), L + 16, L,
+                                                    R, &secs)
+               : noise_gpu_encrypt_uniform_host(key, 11, pt.data(), L, ct.data(), L + 16, L, R, &secs);
+  CHECK(rc == NOISE_GPU_OK, "%s: unaligned encrypt_uniform_host rc=%d", what, rc);
+  std::vector<uint8_t> w(L + 16);
+  for (uint32_t i = 0; i < R; ++i) {
+    oracle_noise_encrypt(key, 11 + i, nullptr, 0, pt.data() + (size_t)i * L, L, w.data());
+    CHECK(std::memcmp(ct.data() + (size_t)i * (L + 16), w.data(), L + 16) == 0,
+          "%s: unaligned uniform_host record %u", what, i);
+  }
+  scan("unaligned encrypt_uniform_host", resident);
+  ++calls;
+  rc = ctx ? noise_gpu_ctx_decrypt_uniform_host(ctx, key, 11, ct.data(), L + 16, back.data(), L, L,
+                                                st.data(), R, &secs)
+           : noise_gpu_decrypt_uniform_host(key, 11, ct.data(), L + 16, back.data(), L, L, st.data(),
+                                            R, &secs);
+  CHECK(rc == NOISE_GPU_OK && back == pt, "%s: unaligned decrypt_uniform_host rc=%d", what, rc);
+  for (uint32_t i = 0; i < R; ++i) CHECK(st[i] == 0, "%s: unaligned uniform_host status %u", what, i);
+  scan("unaligned decrypt_uniform_host", resident);
+}
+
 int main() {
   start_watchdog();
   std::mt19937_64 rng(12345);
@@ -342,9 +376,12 @@ int main() {
   }
   // ---- uniform batch between host buffers (pipeline; the tile kernel's
   // wire-order gather below 1 KiB, the record-wise one from 1 KiB), at
-  // every length the tile kernel serves: G = 1 .. 64 lanes per record
-  for (uint32_t L : {64u, 128u, 192u, 256u, 512u, 1024u, 2048u, 4096u, 8192u, 16384u}) {
-    const uint32_t R = L >= 4096 ? 70 : 300;
+  // every length the tile kernel serves: G = 1 .. 64 lanes per record; and
+  // L = 1000 with packed strides: unaligned, so the chunk is staged through
+  // the scratch of the pipeline's stream in two slices (1024 + 76 records),
+  // which the call must leave zero like the chunk itself
+  for (uint32_t L : {64u, 128u, 192u, 256u, 512u, 1000u, 1024u, 2048u, 4096u, 8192u, 16384u}) {
+    const uint32_t R = L == 1000 ? 1100 : L >= 4096 ? 70 : 300;
     const auto pt = rbytes((size_t)L * R);
     std::vector<uint8_t> ct((size_t)(L + 16) * R), back((size_t)L * R), st(R, 9);
     double secs = 0;
@@ -426,8 +463,11 @@ int main() {
             "ctx encrypt_records_host rc=%d", rc);
       scan("ctx encrypt_records_host", true);
     }
+    // the pipeline streams' staging scratch is the context's too
+    unaligned_uniform(ctx, key, 777, "ctx", true);
     CHECK(noise_gpu_ctx_destroy(ctx) == NOISE_GPU_OK, "ctx_destroy");
-    // destroy freed everything the context allocated, records scratch included
+    // destroy freed everything the context allocated, the scratch of its
+    // staging and pipeline streams included
     CHECK(emu::allocations().size() == live0, "ctx_destroy left %zu allocations",
           emu::allocations().size() - live0);
     CHECK(noise_gpu_ctx_encrypt_host(nullptr, key, 0, nullptr, 0, nullptr, 0) == NOISE_GPU_E_ARG,
@@ -441,6 +481,14 @@ int main() {
                                          NOISE_GPU_UNIFORM_HOST_MAX_LEN + 32,
                                          NOISE_GPU_UNIFORM_HOST_MAX_LEN + 16, 1, &secs) == NOISE_GPU_E_ARG,
           "uniform_host above the maximum length");
+  }
+  // a thread that ends without noise_gpu_thread_release: its contexts'
+  // destructors free what it allocated, its pipeline streams' scratch included
+  {
+    const size_t live0 = emu::allocations().size();
+    std::thread([&] { unaligned_uniform(nullptr, key, 778, "thread exit", false); }).join();
+    CHECK(emu::allocations().size() == live0, "thread exit left %zu allocations",
+          emu::allocations().size() - live0);
   }
   // every per-thread context released: nothing the engine allocated is left
   CHECK(noise_gpu_thread_release() == NOISE_GPU_OK, "thread_release");
