@@ -14,6 +14,7 @@
 #include "launchers.hpp"
 #include "mtile_kernel.hpp"
 #include "tile_kernel.hpp"
+#include "tile_launch.hpp"
 
 namespace noise_amd {
 
@@ -155,12 +156,82 @@ __global__ __launch_bounds__(kBlock) void k_stage_out(const uint8_t *s, uint64_t
   }
 }
 
-// records per call from which staging beats the lane walk; scratch per slice
-constexpr uint64_t kStageMin = 1024;
+// scratch per slice of a staged batch
 #ifndef NOISE_STAGE_BYTES
 #define NOISE_STAGE_BYTES (1ull << 30)
 #endif
 constexpr uint64_t kStageBytes = NOISE_STAGE_BYTES;
+
+#ifndef NOISE_UNIFORM_SPAN  // bytes per lane of the uniform tile kernels (A/B: 128)
+#define NOISE_UNIFORM_SPAN 256
+#endif
+
+// the LDS-staged tile kernel: aligned, AD-free records of an exact length
+static hipError_t launch_uniform_exact(bool decrypt, const TileArgs &ta, uint32_t len, bool contig,
+                                       hipStream_t stream) {
+  for_exact_len(len, [&](auto L) {
+    for_bools(decrypt, contig, [&](auto DEC, auto CONTIG) {
+      constexpr int LEN = decltype(L)::value;
+      hipLaunchKernelGGL((k_aead_tile<decltype(DEC)::value, LEN, decltype(CONTIG)::value, kTileUniform, 0, 1,
+                                      (LEN >= 256 && LEN <= 8192) ? NOISE_UNIFORM_SPAN : 256>),
+                         tile_grid(ta.nrec), dim3(64), 0, stream, ta);
+    });
+  });
+  return hipGetLastError();
+}
+
+// the masked tile kernel (mtile_kernel.hpp) at capacity cap >= len: aligned,
+// AD-free records of any other length up to 16 KiB
+static hipError_t launch_uniform_masked(bool decrypt, TileArgs ta, uint32_t len, uint32_t cap,
+                                        hipStream_t stream) {
+  ta.len = len;
+  ta.chunk = -1;
+  for_len(MaskedCaps{}, cap, [&](auto L) {
+    for_bool(decrypt, [&](auto DEC) {
+      constexpr int CAP = decltype(L)::value;
+      constexpr uint64_t rps = MTileCfg<CAP>::RPS;
+      hipLaunchKernelGGL((k_aead_mtile<decltype(DEC)::value, CAP, kMTUniform>),
+                         dim3((unsigned)((ta.nrec + rps - 1) / rps)), dim3(64), 0, stream, ta);
+    });
+  });
+  return hipGetLastError();
+}
+
+// unaligned records up to 16 KiB, no AD (the batch b): staged through an
+// aligned image (k_stage_in / k_stage_out above), the tile kernels in place on
+// it, in slices of at most kStageBytes of scratch (stream-ordered reuse)
+static hipError_t launch_uniform_staged(bool decrypt, const TileArgs &b, uint32_t len, bool inplace,
+                                        hipStream_t stream) {
+  const uint64_t nrec = b.nrec;
+  const uint64_t sstride = ((uint64_t)len + 31u) & ~15ull;
+  const uint64_t per = kStageBytes / sstride > kStageMin ? kStageBytes / sstride : kStageMin;
+  const uint64_t cap = nrec < per ? nrec : per;
+  void *mem = nullptr;
+  hipError_t e = records_scratch_get(&mem, cap * sstride, stream);
+  if (e != hipSuccess) return e;
+  uint8_t *s = static_cast<uint8_t *>(mem);
+  const uint32_t nin = decrypt ? len + 16u : len, nout = decrypt ? len : len + 16u;
+  const uint32_t np = (nin + 15u) / 16u, nb = nout / 16u + 2u;
+  for (uint64_t r0 = 0; r0 < nrec; r0 += cap) {
+    const uint64_t n = nrec - r0 < cap ? nrec - r0 : cap;
+    hipLaunchKernelGGL(k_stage_in, grid_for(n * np), dim3(kBlock), 0, stream, b.in + r0 * b.in_stride,
+                       b.in_stride, s, sstride, nin, np, n);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    // the image: aligned rows, in place, never packed (sstride >= len + 16)
+    uint8_t *status = b.status ? b.status + r0 : nullptr;
+    TileArgs ta = tile_args_strided(s, sstride, s, sstride, status, n);
+    ta.key = b.key;
+    ta.nonce0 = b.nonce0 + r0;
+    e = exact_index(len) >= 0 ? launch_uniform_exact(decrypt, ta, len, false, stream)
+                              : launch_uniform_masked(decrypt, ta, len, ceil_capacity(MaskedCaps{}, len), stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_stage_out, grid_for(n * nb), dim3(kBlock), 0, stream, s, sstride,
+                       b.out + r0 * b.out_stride, b.out_stride, nout, nb, decrypt ? status : nullptr,
+                       inplace ? 1 : 0, n);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 
 hipError_t launch_aead_uniform(bool decrypt, const uint32_t key[8],
                                uint64_t nonce0, const uint8_t *in,
@@ -172,156 +243,31 @@ hipError_t launch_aead_uniform(bool decrypt, const uint32_t key[8],
   if (nrec == 0) return hipSuccess;
   KeyArg k;
   for (int j = 0; j < 8; ++j) k.w[j] = key[j];
-  const bool vec = ((reinterpret_cast<uintptr_t>(in) |
-                     reinterpret_cast<uintptr_t>(out) | in_stride |
-                     out_stride | len) & 15u) == 0;
-  // LDS-staged tile kernel: aligned, AD-free, supported lengths
-  if (vec && ad_len == 0) {
-    TileArgs ta{};
-    ta.key = k;
-    ta.nonce0 = nonce0;
-    ta.in = in;
-    ta.in_stride = in_stride;
-    ta.out = out;
-    ta.out_stride = out_stride;
-    ta.status = status;
-    ta.nrec = nrec;
-    ta.in_place = in == out;
-    const dim3 gt((unsigned)((nrec + 63) / 64)), bt(64);
-    // packed records (stride == record size on both sides): cheap addressing
-    const bool contig = decrypt ? (in_stride == (uint64_t)len + 16 && out_stride == len)
-                                : (in_stride == len && out_stride == (uint64_t)len + 16);
-#ifndef NOISE_UNIFORM_SPAN  // bytes per lane of the uniform tile kernels (A/B: 128)
-#define NOISE_UNIFORM_SPAN 256
-#endif
-#define NOISE_TILE_LAUNCH(DEC, LEN, CONTIG)                                    \
-    hipLaunchKernelGGL((k_aead_tile<DEC, LEN, CONTIG, kTileUniform, 0, 1,       \
-                                    (LEN >= 256 && LEN <= 8192) ? NOISE_UNIFORM_SPAN : 256>), \
-                       gt, bt, 0, stream, ta)
-#define NOISE_TILE_CASE(LEN)                                                   \
-    case LEN:                                                                  \
-      if (decrypt) {                                                           \
-        if (contig) NOISE_TILE_LAUNCH(true, LEN, true);                        \
-        else NOISE_TILE_LAUNCH(true, LEN, false);                              \
-      } else {                                                                 \
-        if (contig) NOISE_TILE_LAUNCH(false, LEN, true);                       \
-        else NOISE_TILE_LAUNCH(false, LEN, false);                             \
-      }                                                                        \
-      return hipGetLastError();
-    switch (len) {
-      NOISE_TILE_CASE(64)
-      NOISE_TILE_CASE(128)
-      NOISE_TILE_CASE(192)
-      NOISE_TILE_CASE(256)
-      NOISE_TILE_CASE(512)
-      NOISE_TILE_CASE(1024)
-      NOISE_TILE_CASE(2048)
-      NOISE_TILE_CASE(4096)
-      NOISE_TILE_CASE(8192)
-      NOISE_TILE_CASE(16384)
-      default: break;
-    }
-#undef NOISE_TILE_CASE
-#undef NOISE_TILE_LAUNCH
-  }
-  // any other length up to 16 KiB with 16-byte aligned bases and strides:
-  // the masked tile kernel at the smallest tile capacity >= len
-  // (mtile_kernel.hpp).  Capacities between the
-  // powers of two: one lane of 5 .. 7 chunks per record (320 .. 448 B), or
-  // G = 3, 5, 6, 7, 9, 10, 12, 20 lanes of 4 chunks with 60-63 of 64 lanes
-  // working.  The cost of a record ~ capacity x 64 / working lanes rises with
-  // the capacity along this list, so the smallest that holds len is the
-  // cheapest.  (Not listed: 3840, 5376, 7680 -- they idle enough lanes to
-  // cost as much as the next power of two -- and nothing between 8 and 16 KiB,
-  // where a tile holds one record and the idle lanes would be 1/8 .. 1/2.)
-  const bool al = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out) | in_stride |
-                    out_stride) & 15u) == 0;
-  if (al && ad_len == 0 && len >= 1 && len <= 16384) {
-    TileArgs ta{};
-    ta.key = k;
-    ta.nonce0 = nonce0;
-    ta.in = in;
-    ta.in_stride = in_stride;
-    ta.out = out;
-    ta.out_stride = out_stride;
-    ta.status = status;
-    ta.nrec = nrec;
-    ta.in_place = in == out;
-    ta.len = len;
-    ta.chunk = -1;
-#define NOISE_MTILE(LEN)                                                       \
-    if (len <= LEN) {                                                          \
-      constexpr uint64_t rps = MTileCfg<LEN>::RPS;                             \
-      const dim3 gm((unsigned)((nrec + rps - 1) / rps)), bm(64);               \
-      if (decrypt) hipLaunchKernelGGL((k_aead_mtile<true, LEN, kMTUniform>), gm, bm, 0, stream, ta); \
-      else hipLaunchKernelGGL((k_aead_mtile<false, LEN, kMTUniform>), gm, bm, 0, stream, ta);        \
-      return hipGetLastError();                                                \
-    }
-    NOISE_MTILE(64)
-    NOISE_MTILE(128)
-    NOISE_MTILE(192)
-    NOISE_MTILE(256)
-    NOISE_MTILE(320)
-    NOISE_MTILE(384)
-    NOISE_MTILE(448)
-    NOISE_MTILE(512)
-    NOISE_MTILE(768)
-    NOISE_MTILE(1024)
-    NOISE_MTILE(1280)
-    NOISE_MTILE(1536)
-    NOISE_MTILE(1792)
-    NOISE_MTILE(2048)
-    NOISE_MTILE(2304)
-    NOISE_MTILE(2560)
-    NOISE_MTILE(3072)
-    NOISE_MTILE(4096)
-    NOISE_MTILE(5120)
-    NOISE_MTILE(8192)
-    NOISE_MTILE(16384)
-#undef NOISE_MTILE
-  }
-  // unaligned records up to 16 KiB, no AD: staged through an aligned image
-  // (k_stage_in / k_stage_out above), the tile kernels in place on it
+  const uint64_t align_bits =
+      reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out) | in_stride | out_stride;
   const bool inplace = in == out && in_stride == out_stride;
-  if (!al && ad_len == 0 && len >= 1 && len <= 16384 && nrec >= kStageMin &&
-      (inplace || in + in_stride * nrec <= out || out + out_stride * nrec <= in)) {
-    // in slices of at most kStageBytes of scratch (stream-ordered reuse)
-    const uint64_t sstride = ((uint64_t)len + 31u) & ~15ull;
-    const uint64_t per = kStageBytes / sstride > kStageMin ? kStageBytes / sstride : kStageMin;
-    const uint64_t cap = nrec < per ? nrec : per;
-    void *mem = nullptr;
-    hipError_t e = records_scratch_get(&mem, cap * sstride, stream);
-    if (e != hipSuccess) return e;
-    uint8_t *s = static_cast<uint8_t *>(mem);
-    const uint32_t nin = decrypt ? len + 16u : len, nout = decrypt ? len : len + 16u;
-    const uint32_t np = (nin + 15u) / 16u, nb = nout / 16u + 2u;
-    for (uint64_t r0 = 0; r0 < nrec; r0 += cap) {
-      const uint64_t n = nrec - r0 < cap ? nrec - r0 : cap;
-      hipLaunchKernelGGL(k_stage_in, grid_for(n * np), dim3(kBlock), 0, stream, in + r0 * in_stride, in_stride,
-                         s, sstride, nin, np, n);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-      e = launch_aead_uniform(decrypt, key, nonce0 + r0, s, sstride, s, sstride, len, nullptr, 0, 0,
-                              status ? status + r0 : nullptr, n, stream);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(k_stage_out, grid_for(n * nb), dim3(kBlock), 0, stream, s, sstride,
-                         out + r0 * out_stride, out_stride, nout, nb, decrypt ? status + r0 : nullptr,
-                         inplace ? 1 : 0, n);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    return hipSuccess;
+  const bool disjoint = in + in_stride * nrec <= out || out + out_stride * nrec <= in;
+  const UniformPath path = uniform_path(decrypt, len, ad_len, align_bits, nrec, inplace, disjoint);
+  TileArgs ta = tile_args_strided(in, in_stride, out, out_stride, status, nrec);
+  ta.key = k;
+  ta.nonce0 = nonce0;
+  switch (path.kind) {
+    case UniformKind::kExactTile:
+      return launch_uniform_exact(decrypt, ta, len, packed_strides(decrypt, len, in_stride, out_stride), stream);
+    case UniformKind::kMaskedTile:
+      return launch_uniform_masked(decrypt, ta, len, path.cap, stream);
+    case UniformKind::kStaged:
+      return launch_uniform_staged(decrypt, ta, len, inplace, stream);
+    case UniformKind::kLaneVec:
+    case UniformKind::kLaneScalar:
+      break;
   }
-  const dim3 g = grid_for(nrec), b(kBlock);
-  if (decrypt) {
-    if (vec)
-      hipLaunchKernelGGL((k_aead_uniform<true, true>), g, b, 0, stream, k, nonce0, in, in_stride, out, out_stride, len, ad, ad_stride, ad_len, status, nrec);
-    else
-      hipLaunchKernelGGL((k_aead_uniform<true, false>), g, b, 0, stream, k, nonce0, in, in_stride, out, out_stride, len, ad, ad_stride, ad_len, status, nrec);
-  } else {
-    if (vec)
-      hipLaunchKernelGGL((k_aead_uniform<false, true>), g, b, 0, stream, k, nonce0, in, in_stride, out, out_stride, len, ad, ad_stride, ad_len, status, nrec);
-    else
-      hipLaunchKernelGGL((k_aead_uniform<false, false>), g, b, 0, stream, k, nonce0, in, in_stride, out, out_stride, len, ad, ad_stride, ad_len, status, nrec);
-  }
+  // one lane per record (chachapoly_device.hpp)
+  for_bools(decrypt, path.kind == UniformKind::kLaneVec, [&](auto DEC, auto VEC) {
+    hipLaunchKernelGGL((k_aead_uniform<decltype(DEC)::value, decltype(VEC)::value>), grid_for(nrec), dim3(kBlock),
+                       0, stream, k, nonce0, in, in_stride, out, out_stride, len, ad, ad_stride, ad_len,
+                       status, nrec);
+  });
   return hipGetLastError();
 }
 

@@ -140,7 +140,7 @@ __device__ __forceinline__ void store_head(uint8_t *p, uint4 v, uint32_t n) {
 // lane per record, CPL = L / 64.  Above: lanes of 4 chunks (256 B), G = L / 256
 // lanes per record -- G need not divide 64 (1280 B: G = 5, 12 records on 60
 // lanes; lanes past RPT G idle), which gives capacities between the powers of
-// two (the uniform dispatch, aead_kernels.hip).
+// two (the uniform path's MaskedCaps, tile_classes.hpp).
 template <int L>
 struct MTileCfg {
   static constexpr int NCH = L / 64;

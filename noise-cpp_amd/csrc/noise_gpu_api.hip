@@ -20,6 +20,7 @@
 #include "launchers.hpp"
 #include "noise_amd/dev_mem.hpp"
 #include "noise_gpu.h"
+#include "tile_classes.hpp"
 
 namespace {
 
@@ -744,9 +745,11 @@ static int sessions(bool decrypt, const uint8_t *d_keys, uint32_t nkeys,
   int rc = check_uniform(decrypt, d_in, in_stride, d_out, out_stride, len,
                          nullptr, 0, d_status, nrec);
   if (rc) return rc;
-  if (!noise_amd::sessions_supported(len, d_in, in_stride, d_out, out_stride))
-    return arg_fail("sessions batches need len in {64,128,192,256,512,1024,2048,4096,8192,16384} "
-                    "and 16-byte aligned buffers/strides");
+  if (!noise_amd::sessions_supported(len, d_in, in_stride, d_out, out_stride)) {
+    std::string lens;
+    for (uint32_t l : noise_amd::ExactLens::v) lens += (lens.empty() ? "" : ",") + std::to_string(l);
+    return arg_fail(("sessions batches need len in {" + lens + "} and 16-byte aligned buffers/strides").c_str());
+  }
   if ((rc = check_device())) return rc;
   HIP_TRY(noise_amd::launch_aead_sessions(decrypt, d_keys, nkeys, d_key_idx,
                                           d_nonces, d_in, in_stride, d_out,

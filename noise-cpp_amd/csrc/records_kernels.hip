@@ -37,27 +37,12 @@
 #include "launchers.hpp"
 #include "mtile_kernel.hpp"
 #include "tile_kernel.hpp"
+#include "tile_launch.hpp"
 
 namespace noise_amd {
 
 constexpr int kGenBlock = 256;
-constexpr int kNumTileCls = 10;           // exactly 64 128 192 256 512 1024 2048 4096 8192 16384
-constexpr int kMCls0 = kNumTileCls;       // the masked (ragged) classes: any other length up to
-constexpr int kNumMCls = 10;              //   the same ten capacities (mtile_kernel.hpp)
-static_assert(kNumMCls == kNumTileCls, "one ragged class per exact tile class");
-// idx order: exact class c, then the ragged class of the same capacity (one
-// masked-kernel launch takes both: launch_classes), then long and generic
-__host__ __device__ constexpr int cls_order(int k) {
-  return k < 2 * kNumTileCls ? ((k & 1) ? kMCls0 + k / 2 : k / 2) : k;
-}
-constexpr int kClsLong = kMCls0 + kNumMCls;  // segmented long records (> 16 KiB)
-constexpr int kClsGeneric = kClsLong + 1;
-constexpr int kNumCls = kClsLong + 2;
-constexpr int kColSegs = kNumCls;         // classifier column: full segments
-constexpr int kColTails = kNumCls + 1;    // classifier column: long records with a tail
-constexpr int kColFin0 = kNumCls + 2;     // classifier columns: long records by
-constexpr int kFinBuckets = 6;            // floor(log2(full segments)), 1..63 -> 0..5
-constexpr int kCols = kNumCls + 2 + kFinBuckets;
+// the classes and the classifier's columns (kNumTileCls .. kCols): tile_classes.hpp
 // Decrypt pipelines the long records in kSegChunks chunks (launch_classes):
 // the Poly1305 pass of chunk c + 1 (HBM-bound) runs beside the keystream pass
 // of chunk c (VALU-bound).  Chunk boundaries fall on record starts, near
@@ -106,7 +91,6 @@ static_assert(kClsWaves % 64 == 0 && kClsMinChunk % 64 == 0, "classifier geometr
 #endif
 constexpr uint64_t kClassifyMin = NOISE_CLASSIFY_MIN;
 constexpr uint64_t kClassifyAvgLen = 2048;  // below kClassifyMin: classify when records average this
-constexpr uint32_t kLongMax = 65535;      // the Noise message bound
 #ifndef NOISE_SEG_CAP  // overridable for the CPU emulation build (overflow path)
 #define NOISE_SEG_CAP (1ull << 24)
 #endif
@@ -128,17 +112,9 @@ __device__ __forceinline__ bool key_row_zero(const uint8_t *keys, uint32_t ki) {
   return (a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w) == 0u;
 }
 
-// (NOISE_SEG_LO, NOISE_SEG_MID_HI] (not an exact tile size): segments
-// instead of the masked tile of the next capacity
-#ifndef NOISE_SEG_LO
-#define NOISE_SEG_LO 2048
-#endif
-#ifndef NOISE_SEG_MID_HI
-#define NOISE_SEG_MID_HI 16383
-#endif
-
 // records the tile / segment kernels cannot take go to the generic class,
-// which also reports bad key rows (index out of range or all zero)
+// which also reports bad key rows (index out of range or all zero); the
+// others by their length (len_class, tile_classes.hpp)
 __device__ __forceinline__ int record_class(const noise_gpu_record &d, const uint8_t *keys,
                                             uint32_t nkeys, const uint8_t *in,
                                             const uint8_t *out) {
@@ -147,38 +123,7 @@ __device__ __forceinline__ int record_class(const noise_gpu_record &d, const uin
   if (((reinterpret_cast<uintptr_t>(in + d.in_off) |
         reinterpret_cast<uintptr_t>(out + d.out_off)) & 15u) != 0)
     return kClsGeneric;
-  switch (d.len) {
-    case 64: return 0;
-    case 128: return 1;
-    case 192: return 2;
-    case 256: return 3;
-    case 512: return 4;
-    case 1024: return 5;  // exactly 1 KiB: one tile-kernel pass beats prep + segment + finalize
-    // whole-record tiles up to 16 KiB (one 16 KiB LDS tile per record at
-    // 16 KiB): the tag is computed and checked in the wave that holds the
-    // record, so decrypt reads it once -- the segment path's verify-first
-    // decrypt reads a long record's ciphertext twice (§4.3 of DESIGN.md)
-    case 2048: return 6;
-    case 4096: return 7;
-    case 8192: return 8;
-    case 16384: return 9;
-    default: break;
-  }
-  // every other length up to 16 KiB: the masked tile class of the smallest
-  // capacity that holds it -- the record still sits whole in one wave's
-  // tile, so decrypt checks its tag there and reads the ciphertext once
-  // Above 2 KiB (but the exact 4, 8, 16 KiB tiles) the segment path (1 KiB
-  // segments + a masked tail unit) beats the masked tile of the next
-  // capacity: single-length batches of 3000 / 5000 / 9000 / 16000 B at
-  // 1131 / 1205 / 1223 / 1219 GiB/s against 983 / 813 / 693 / 1148, config 4
-  // within its noise (profiles/round6/ab/seg_threshold.md)
-  if (d.len <= 16384u && !(d.len > (uint32_t)NOISE_SEG_LO && d.len <= (uint32_t)NOISE_SEG_MID_HI)) {
-    const uint32_t n = d.len;
-    const int c = n <= 64u ? 0 : n <= 128u ? 1 : n <= 192u ? 2 : n <= 256u ? 3 : n <= 512u ? 4
-                : n <= 1024u ? 5 : n <= 2048u ? 6 : n <= 4096u ? 7 : n <= 8192u ? 8 : 9;
-    return kMCls0 + c;
-  }
-  return d.len <= kLongMax ? kClsLong : kClsGeneric;
+  return len_class(d.len);
 }
 
 // device header of the scratch buffer
@@ -709,6 +654,77 @@ static inline unsigned capped(uint64_t want, uint64_t cap) {
   return (unsigned)(want < cap ? want : cap);
 }
 
+// one records call: the arguments of launch_aead_records
+struct RecCall {
+  const uint8_t *keys;
+  uint32_t nkeys;
+  const noise_gpu_record *recs;
+  uint64_t nrec;
+  const uint8_t *in;
+  uint8_t *out;
+  const uint8_t *ad;
+  uint8_t *status;
+  hipStream_t stream;
+};
+
+// The scratch block of a classified call:
+//   header | part[nw][kCols] | wbase[nw][kCols] | idx[nrec] | tails[nrec] |
+//   fin[nrec] | rt[nrec] | segs[segcap] | partial[segcap] | partial_hi[segcap]
+// each array 256-byte aligned.  base == nullptr: only `bytes` means anything.
+struct RecScratch {
+  RecHdr *hdr;
+  uint32_t *part;             // classifier: per-wave partial counts
+  unsigned long long *wbase;  // classifier: per-wave bases
+  uint32_t *idx;              // descriptor indices in class order
+  uint32_t *tails, *fin;      // long records with a tail / in finalize order (SegRec indices)
+  SegRec *rt;
+  SegEntry *segs;
+  SegPartial *partial;
+  uint32_t *partial_hi;
+  uint64_t segcap;  // segments the last three arrays hold
+  uint64_t bytes = 0;
+
+  RecScratch(void *base, uint64_t nrec, uint64_t nw, uint64_t segcap) : segcap(segcap) {
+    uint64_t o = 0;
+    auto take = [&](auto *&p, uint64_t n) {
+      p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(reinterpret_cast<uintptr_t>(base) + o);
+      bytes = o + n * sizeof(*p);
+      o = align_up(bytes, 256);
+    };
+    take(hdr, 1);
+    take(part, nw * kCols);
+    take(wbase, nw * kCols);
+    take(idx, nrec);
+    take(tails, nrec);
+    take(fin, nrec);
+    take(rt, nrec);
+    take(segs, segcap);
+    take(partial, segcap);
+    take(partial_hi, segcap);
+  }
+};
+
+// what every tile-kernel launch of a descriptor batch shares (tile_args_strided's
+// sibling, tile_launch.hpp)
+static TileArgs tile_args_desc(const RecCall &c, const RecScratch &s) {
+  TileArgs a{};
+  a.in = c.in;
+  a.out = c.out;
+  a.status = c.status;
+  a.keys = c.keys;
+  a.nkeys = c.nkeys;
+  a.recs = c.recs;
+  a.idx = s.idx;
+  a.cls_base = s.hdr->cls_base;
+  a.counts = s.hdr->counts;
+  a.segs = s.segs;
+  a.rt = s.rt;
+  a.partial = s.partial;
+  a.partial_hi = s.partial_hi;
+  a.nseg = &s.hdr->nseg;
+  return a;
+}
+
 // After the classifier, two branches.  Encrypt:
 //   caller stream : k_seg_prep -+-> segment tile kernel (kTileSeg) --- join -> finalize
 //   companion     : (fork)  the six small tile classes, the generic kernel,
@@ -736,37 +752,34 @@ static inline unsigned capped(uint64_t want, uint64_t cap) {
 // (A third companion for the tails' plaintext, so that it does not queue
 // behind the small classes, measured 1-2 % slower: round 5.)
 template <bool DECRYPT>
-static hipError_t launch_classes(const TileArgs &ta, uint64_t nrec, const RecHdr *hdr,
-                                 const uint8_t *keys, uint32_t nkeys,
-                                 const noise_gpu_record *recs, const uint32_t *idx,
-                                 const uint32_t *tails, const uint32_t *fin, uint64_t segbound,
-                                 const uint8_t *in,
-                                 uint8_t *out, const uint8_t *ad, uint8_t *status,
-                                 hipStream_t stream, int chunks) {
-  AuxStream ax;
-  hipError_t e = records_aux_get(&ax, stream);
-  if (e != hipSuccess) return e;
+static hipError_t launch_classes(const RecCall &c, const RecScratch &s, const AuxStream &ax, int chunks) {
+  hipError_t e = hipSuccess;
+  // true: failed (e holds the error)
+  auto record = [&e](hipEvent_t ev, hipStream_t st) { return (e = hipEventRecord(ev, st)) != hipSuccess; };
+  auto wait = [&e](hipStream_t st, hipEvent_t ev) { return (e = hipStreamWaitEvent(st, ev, 0)) != hipSuccess; };
+  const hipStream_t stream = c.stream;
+  const uint64_t nrec = c.nrec;
+  const RecHdr *hdr = s.hdr;
   const dim3 bt(64);
   const dim3 grid(capped((nrec + 63) / 64, NOISE_GRID_CAP));
   // a class launch: enough workgroups for the whole batch in the class (its
   // size is on the device), RPS records per super-tile -- 8 for 16 KiB, so a
   // batch of 100 K such records makes 12.5 K waves, not 1.6 K
   auto desc_grid = [nrec](uint64_t rps) { return dim3(capped((nrec + rps - 1) / rps, NOISE_GRID_CAP)); };
-  SegRec *rt = const_cast<SegRec *>(ta.rt);
   // fork right after the classifier: the small classes and the generic
   // kernel need nothing else; the tails also need k_seg_prep (prep event)
-  if ((e = hipEventRecord(ax.fork, stream)) != hipSuccess) return e;
-  if ((e = hipStreamWaitEvent(ax.aux, ax.fork, 0)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_seg_prep, grid, bt, 0, stream, keys, rt, hdr);
-  if ((e = hipEventRecord(ax.prep, stream)) != hipSuccess) return e;
-  TileArgs a = ta;
+  if (record(ax.fork, stream) || wait(ax.aux, ax.fork)) return e;
+  hipLaunchKernelGGL(k_seg_prep, grid, bt, 0, stream, c.keys, s.rt, hdr);
+  if (record(ax.prep, stream)) return e;
+  TileArgs a = tile_args_desc(c, s);  // each launch sets its own class, chunk or tail fields
   const uint64_t gblocks = (nrec + kGenBlock - 1) / kGenBlock;
   const dim3 gg((unsigned)(gblocks < 2 * NOISE_GRID_CAP ? gblocks : 2 * NOISE_GRID_CAP));
-  const dim3 gseg(capped((segbound + 63) / 64, NOISE_GRID_CAP));
-  const dim3 gpoly(capped((segbound + 63) / 64, NOISE_GRID_CAP));
-  const dim3 gxor(capped((segbound + 63) / 64, NOISE_GRID_CAP));
+  const dim3 gseg(capped((s.segcap + 63) / 64, NOISE_GRID_CAP));
   const dim3 gfin(capped((nrec + 64 / NOISE_FIN_W - 1) / (64 / NOISE_FIN_W), NOISE_GRID_CAP));
-  RecHdr *hdr_w = const_cast<RecHdr *>(hdr);
+  auto finalize = [&](int chunk) {
+    hipLaunchKernelGGL((k_seg_finalize_w<DECRYPT, NOISE_FIN_W>), gfin, bt, 0, stream, s.fin, s.rt, s.partial,
+                       s.partial_hi, s.hdr, c.in, c.out, c.status, chunk);
+  };
   // one launch per capacity: the exact-size records of the class and the
   // ragged ones of the same capacity (adjacent in idx, cls_order), the
   // masked kernel switching to its exact-size body per super-tile.  Two
@@ -774,27 +787,25 @@ static hipError_t launch_classes(const TileArgs &ta, uint64_t nrec, const RecHdr
   // nearly empty launches queued between full ones: a capped grid of single
   // -wave workgroups waits for CU slots even when it has no work (config-4
   // traces, profiles/round6/merged/cfg4_*_timeline.txt).
-#define NOISE_DESC_BIG(ST)                                                     \
-  NOISE_DESC_CAP(9, 16384, ST)                                                 \
-  NOISE_DESC_CAP(8, 8192, ST)                                                  \
-  NOISE_DESC_CAP(7, 4096, ST)                                                  \
-  NOISE_DESC_CAP(6, 2048, ST)
-#define NOISE_DESC_TILES()                                                     \
-  NOISE_DESC_CAP(0, 64, ax.aux)                                                \
-  NOISE_DESC_CAP(1, 128, ax.aux)                                               \
-  NOISE_DESC_CAP(2, 192, ax.aux)                                               \
-  NOISE_DESC_CAP(3, 256, ax.aux)                                               \
-  NOISE_DESC_CAP(4, 512, ax.aux)                                               \
-  NOISE_DESC_CAP(5, 1024, ax.aux)                                              \
-  hipLaunchKernelGGL((k_aead_records<DECRYPT>), gg, dim3(kGenBlock), 0, ax.aux, keys, nkeys, recs,  \
-                     nrec, idx, hdr, in, out, ad, status);
-#define NOISE_DESC_CAP(C, LEN, ST)                                             \
-  a.cls = C;                                                                   \
-  a.cls2 = kMCls0 + C;                                                         \
-  hipLaunchKernelGGL((k_aead_mtile<DECRYPT, LEN, kMTDesc>), desc_grid(MTileCfg<LEN>::RPS), bt, 0, ST, a);
+  auto desc_on = [&](hipStream_t st) {
+    return [&, st](auto C, auto L) {
+      a.cls = C;
+      a.cls2 = kMCls0 + C;
+      hipLaunchKernelGGL((k_aead_mtile<DECRYPT, decltype(L)::value, kMTDesc>),
+                         desc_grid(MTileCfg<decltype(L)::value>::RPS), bt, 0, st, a);
+    };
+  };
+  constexpr int kBig0 = exact_index(2048);  // the first whole-record class
+  static_assert(kBig0 == exact_index(1024) + 1, "every exact class on one of the two companions");
+  // the classes up to 1 KiB, smallest first, then the generic kernel
+  auto small_classes_and_generic = [&] {
+    for_exact_classes<0, kBig0 - 1>(desc_on(ax.aux));
+    hipLaunchKernelGGL((k_aead_records<DECRYPT>), gg, dim3(kGenBlock), 0, ax.aux, c.keys, c.nkeys, c.recs, nrec,
+                       s.idx, hdr, c.in, c.out, c.ad, c.status);
+  };
   // the long records' tails (len % 1024 bytes) as masked 1 KiB tile units
   TileArgs at = a;
-  at.tails = tails;
+  at.tails = s.tails;
   at.ntails = &hdr->counts[kColTails];
   at.nlong = &hdr->nlong;
   at.tail_split = nullptr;
@@ -804,33 +815,32 @@ static hipError_t launch_classes(const TileArgs &ta, uint64_t nrec, const RecHdr
   // queue behind (or ahead of) the small classes and the tails
   // (round 5: ahead of encrypt's segment kernel on the caller's stream
   // instead, encrypt took 5 % longer)
-  if ((e = hipStreamWaitEvent(ax.aux3, ax.fork, 0)) != hipSuccess) return e;
-  NOISE_DESC_BIG(ax.aux3)
-  if ((e = hipEventRecord(ax.big, ax.aux3)) != hipSuccess) return e;
+  if (wait(ax.aux3, ax.fork)) return e;
+  for_exact_classes<kNumTileCls - 1, kBig0>(desc_on(ax.aux3));  // 16 KiB first
+  if (record(ax.big, ax.aux3)) return e;
   if (!DECRYPT) {
     // companion: dense tile classes first, the tails (masked 1 KiB units)
     // last.  Round 6 A/B, the tails on companion 2 from the prep event
     // instead: config 4 1391-1395 against 1408-1409 GiB/s (exact lengths),
     // 1330-1336 against 1339-1351 (jittered), same box, alternating
     // (profiles/round6/ab/enc_tails.md)
-    NOISE_DESC_TILES()
-    if ((e = hipStreamWaitEvent(ax.aux, ax.prep, 0)) != hipSuccess) return e;
+    small_classes_and_generic();
+    if (wait(ax.aux, ax.prep)) return e;
     hipLaunchKernelGGL((k_aead_mtile<false, 1024, kMTTail>), grid, bt, 0, ax.aux, at);
-    if ((e = hipEventRecord(ax.join, ax.aux)) != hipSuccess) return e;
+    if (record(ax.join, ax.aux)) return e;
     // caller: every full segment of every long record, then the tags
     hipLaunchKernelGGL((k_aead_tile<DECRYPT, 1024, false, kTileSeg>), gseg, bt, 0, stream, a);
-    if ((e = hipStreamWaitEvent(stream, ax.join, 0)) != hipSuccess) return e;
-    hipLaunchKernelGGL((k_seg_finalize_w<DECRYPT, NOISE_FIN_W>), gfin, bt, 0, stream, fin, rt, ta.partial,
-                       ta.partial_hi, hdr_w, in, out, status, -1);
-    if ((e = hipStreamWaitEvent(stream, ax.big, 0)) != hipSuccess) return e;
+    if (wait(stream, ax.join)) return e;
+    finalize(-1);
+    if (wait(stream, ax.big)) return e;
     return hipGetLastError();
   }
   // decrypt.  Companion: the tails' Poly1305 first (the first tag check
   // waits for it), then the small classes and the generic kernel
-  if ((e = hipStreamWaitEvent(ax.aux, ax.prep, 0)) != hipSuccess) return e;
+  if (wait(ax.aux, ax.prep)) return e;
   hipLaunchKernelGGL((k_aead_mtile<true, 1024, kMTTailPoly>), grid, bt, 0, ax.aux, at);
-  if ((e = hipEventRecord(ax.join, ax.aux)) != hipSuccess) return e;
-  NOISE_DESC_TILES()
+  if (record(ax.join, ax.aux)) return e;
+  small_classes_and_generic();
   // caller: per chunk, the Poly1305 pass and the tag check (the first one
   // also waits for the tails' P_tail).  The checks sit here, not in front of
   // the keystream passes, so chunk c + 1's is done while chunk c's plaintext
@@ -839,37 +849,30 @@ static hipError_t launch_classes(const TileArgs &ta, uint64_t nrec, const RecHdr
   // classifier's bucket order)
   TileArgs ac = a;
   ac.seg_split = chunks > 1 ? hdr->ssplit : nullptr;
-  auto cidx = [chunks](int c) { return chunks > 1 ? c : -1; };
-  for (int c = 0; c < chunks; ++c) {
-    ac.chunk = cidx(c);
-    hipLaunchKernelGGL((k_aead_tile<true, 1024, false, kTileSegPoly, 0, 1, NOISE_POLY_SPAN>), gpoly, bt, 0,
+  auto cidx = [chunks](int k) { return chunks > 1 ? k : -1; };
+  for (int k = 0; k < chunks; ++k) {
+    ac.chunk = cidx(k);
+    hipLaunchKernelGGL((k_aead_tile<true, 1024, false, kTileSegPoly, 0, 1, NOISE_POLY_SPAN>), gseg, bt, 0,
                        stream, ac);
-    if (c == 0 && (e = hipStreamWaitEvent(stream, ax.join, 0)) != hipSuccess) return e;
-    hipLaunchKernelGGL((k_seg_finalize_w<true, NOISE_FIN_W>), gfin, bt, 0, stream, fin, rt, ta.partial,
-                       ta.partial_hi, hdr_w, in, out, status, cidx(c));
-    if ((e = hipEventRecord(ax.fin[c], stream)) != hipSuccess) return e;
+    if (k == 0 && wait(stream, ax.join)) return e;
+    finalize(cidx(k));
+    if (record(ax.fin[k], stream)) return e;
   }
   // companion 2: the segments' plaintext, chunk by chunk; the companion
   // writes each chunk's tails' plaintext beside it
-  for (int c = 0; c < chunks; ++c) {
-    ac.chunk = cidx(c);
-    if ((e = hipStreamWaitEvent(ax.aux2, ax.fin[c], 0)) != hipSuccess) return e;
-    hipLaunchKernelGGL((k_aead_tile<true, 1024, false, kTileSegXor, 0, 1, NOISE_XOR_SPAN>), gxor, bt, 0,
+  for (int k = 0; k < chunks; ++k) {
+    ac.chunk = cidx(k);
+    if (wait(ax.aux2, ax.fin[k])) return e;
+    hipLaunchKernelGGL((k_aead_tile<true, 1024, false, kTileSegXor, 0, 1, NOISE_XOR_SPAN>), gseg, bt, 0,
                        ax.aux2, ac);
-    if ((e = hipStreamWaitEvent(ax.aux, ax.fin[c], 0)) != hipSuccess) return e;
+    if (wait(ax.aux, ax.fin[k])) return e;
     TileArgs atc = at;
-    atc.chunk = cidx(c);
+    atc.chunk = cidx(k);
     atc.tail_split = chunks > 1 ? hdr->tsplit : nullptr;
     hipLaunchKernelGGL((k_aead_mtile<true, 1024, kMTTailXor>), grid, bt, 0, ax.aux, atc);
   }
-#undef NOISE_DESC_CAP
-#undef NOISE_DESC_TILES
-#undef NOISE_DESC_BIG
-  if ((e = hipEventRecord(ax.xdone, ax.aux2)) != hipSuccess) return e;
-  if ((e = hipEventRecord(ax.join2, ax.aux)) != hipSuccess) return e;
-  if ((e = hipStreamWaitEvent(stream, ax.xdone, 0)) != hipSuccess) return e;
-  if ((e = hipStreamWaitEvent(stream, ax.join2, 0)) != hipSuccess) return e;
-  if ((e = hipStreamWaitEvent(stream, ax.big, 0)) != hipSuccess) return e;
+  if (record(ax.xdone, ax.aux2) || record(ax.join2, ax.aux)) return e;
+  if (wait(stream, ax.xdone) || wait(stream, ax.join2) || wait(stream, ax.big)) return e;
   return hipGetLastError();
 }
 
@@ -888,10 +891,10 @@ hipError_t launch_aead_records(bool decrypt, const uint8_t *keys,
   // classified; 300 x 1 KiB 97 / 282; 100 x 16 KiB 1909 / 353.
   const bool few = nrec < kClassifyMin && !(len_sum && len_sum / nrec >= kClassifyAvgLen);
   if (few) {
-    if (decrypt)
-      hipLaunchKernelGGL((k_aead_records<true>), dim3((unsigned)gblocks), bg, 0, stream, keys, nkeys, recs, nrec, nullptr, nullptr, in, out, ad, status);
-    else
-      hipLaunchKernelGGL((k_aead_records<false>), dim3((unsigned)gblocks), bg, 0, stream, keys, nkeys, recs, nrec, nullptr, nullptr, in, out, ad, status);
+    for_bool(decrypt, [&](auto DEC) {
+      hipLaunchKernelGGL((k_aead_records<decltype(DEC)::value>), dim3((unsigned)gblocks), bg, 0, stream, keys,
+                         nkeys, recs, nrec, nullptr, nullptr, in, out, ad, status);
+    });
     return hipGetLastError();
   }
   if (nrec > 0xffffffffull) return hipErrorInvalidValue;  // 32-bit indices
@@ -902,61 +905,23 @@ hipError_t launch_aead_records(bool decrypt, const uint8_t *keys,
   const uint64_t nw = (nrec + chunk - 1) / chunk;
   const uint64_t segcap = nrec * 63 < kSegCapMax ? nrec * 63 : kSegCapMax;
 
-  // scratch: header | part[nw][kCols] | wbase[nw][kCols] | idx[nrec] |
-  //          tails[nrec] | fin[nrec] | rt[nrec] | segs[segcap] | partial[segcap] |
-  //          partial_hi[segcap]
-  const uint64_t o_part = sizeof(RecHdr);
-  const uint64_t o_wbase = align_up(o_part + nw * kCols * 4, 256);
-  const uint64_t o_idx = align_up(o_wbase + nw * kCols * 8, 256);
-  const uint64_t o_tails = align_up(o_idx + nrec * 4, 256);
-  const uint64_t o_fin = align_up(o_tails + nrec * 4, 256);
-  const uint64_t o_rt = align_up(o_fin + nrec * 4, 256);
-  const uint64_t o_segs = align_up(o_rt + nrec * sizeof(SegRec), 256);
-  const uint64_t o_part2 = align_up(o_segs + segcap * sizeof(SegEntry), 256);
-  const uint64_t o_phi = align_up(o_part2 + segcap * sizeof(SegPartial), 256);
-  const uint64_t bytes = o_phi + segcap * sizeof(uint32_t);
   void *mem = nullptr;
-  hipError_t e = records_scratch_get(&mem, bytes, stream);
+  hipError_t e = records_scratch_get(&mem, RecScratch(nullptr, nrec, nw, segcap).bytes, stream);
   if (e != hipSuccess) return e;
-  uint8_t *base = static_cast<uint8_t *>(mem);
-  RecHdr *hdr = reinterpret_cast<RecHdr *>(base);
-  uint32_t *part = reinterpret_cast<uint32_t *>(base + o_part);
-  unsigned long long *wbase = reinterpret_cast<unsigned long long *>(base + o_wbase);
-  uint32_t *idx = reinterpret_cast<uint32_t *>(base + o_idx);
-  uint32_t *tails = reinterpret_cast<uint32_t *>(base + o_tails);
-  uint32_t *fin = reinterpret_cast<uint32_t *>(base + o_fin);
-  SegRec *rt = reinterpret_cast<SegRec *>(base + o_rt);
-  SegEntry *segs = reinterpret_cast<SegEntry *>(base + o_segs);
-  SegPartial *partial = reinterpret_cast<SegPartial *>(base + o_part2);
-  uint32_t *partial_hi = reinterpret_cast<uint32_t *>(base + o_phi);
+  const RecScratch s(mem, nrec, nw, segcap);
 
   const dim3 b64(64);
-  hipLaunchKernelGGL(k_cls_count, dim3((unsigned)nw), b64, 0, stream, recs, nrec, (uint32_t)chunk, keys, nkeys, in, out, part);
-  hipLaunchKernelGGL(k_cls_scan, dim3(kCols), b64, 0, stream, part, (uint32_t)nw, wbase, hdr, segcap);
-  hipLaunchKernelGGL(k_cls_scatter, dim3((unsigned)nw), b64, 0, stream, recs, nrec, (uint32_t)chunk, keys, nkeys, in, out, wbase, hdr, idx, rt, segs, tails, fin, segcap);
+  hipLaunchKernelGGL(k_cls_count, dim3((unsigned)nw), b64, 0, stream, recs, nrec, (uint32_t)chunk, keys, nkeys, in, out, s.part);
+  hipLaunchKernelGGL(k_cls_scan, dim3(kCols), b64, 0, stream, s.part, (uint32_t)nw, s.wbase, s.hdr, segcap);
+  hipLaunchKernelGGL(k_cls_scatter, dim3((unsigned)nw), b64, 0, stream, recs, nrec, (uint32_t)chunk, keys, nkeys, in, out, s.wbase, s.hdr, s.idx, s.rt, s.segs, s.tails, s.fin, segcap);
 
-  TileArgs ta{};
-  ta.in = in;
-  ta.out = out;
-  ta.status = status;
-  ta.keys = keys;
-  ta.nkeys = nkeys;
-  ta.recs = recs;
-  ta.idx = idx;
-  ta.cls_base = hdr->cls_base;
-  ta.counts = hdr->counts;
-  ta.segs = segs;
-  ta.rt = rt;
-  ta.partial = partial;
-  ta.partial_hi = partial_hi;
-  ta.nseg = &hdr->nseg;
+  AuxStream ax;
+  if ((e = records_aux_get(&ax, stream)) != hipSuccess) return e;
+  const RecCall call{keys, nkeys, recs, nrec, in, out, ad, status, stream};
   // the decrypt pipeline's chunks pay off on large batches only (each chunk
   // adds four launches and a stream hand-off)
-  const int chunks = nrec >= kChunkMinRecords ? kSegChunks : 1;
-  return decrypt ? launch_classes<true>(ta, nrec, hdr, keys, nkeys, recs, idx, tails, fin, segcap,
-                                       in, out, ad, status, stream, chunks)
-                 : launch_classes<false>(ta, nrec, hdr, keys, nkeys, recs, idx, tails, fin, segcap,
-                                         in, out, ad, status, stream, 1);
+  return decrypt ? launch_classes<true>(call, s, ax, nrec >= kChunkMinRecords ? kSegChunks : 1)
+                 : launch_classes<false>(call, s, ax, 1);
 }
 
 }  // namespace noise_amd

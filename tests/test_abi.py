@@ -181,3 +181,17 @@ def test_resident_request_tag_survives_tears(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "decode to the new seq" in r.stdout and ", 0 decode" in r.stdout
+
+
+def test_tile_class_tables_and_choices(tmp_path):
+    """The tile capacity tables and the pure choices over them
+    (csrc/tile_classes.hpp: exact lengths, masked capacities, len_class,
+    ceil_capacity, uniform_path) against the rules restated in
+    tests/cpp/tile_classes_test.cpp (host-only)."""
+    exe = str(tmp_path / "tile_classes_test")
+    subprocess.run(["g++", "-std=c++20", "-O1", "-pthread", "-I", os.path.join(ROOT, "tools", "emu", "include"),
+                    "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "noise-cpp_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "cpp", "tile_classes_test.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "cases checked, 0 wrong" in r.stdout

@@ -18,7 +18,7 @@ def main():
     torch.cuda.set_device(0)
     bench.noise_amd.load()
     stream = torch.cuda.current_stream()
-    args = types.SimpleNamespace(records=None, rec_align=16)
+    args = types.SimpleNamespace(records=None, rec_align=16, jitter=False, dump_outputs=None)
     wl = bench.make_workload(4, args, 0, 1, stream)
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
     for _ in range(5):
