@@ -333,6 +333,92 @@ int noise_gpu_hs_status(const noise_gpu_hs *hs, uint8_t *d_status, void *stream)
 int noise_gpu_hs_split(noise_gpu_hs *hs, uint8_t *d_k1, uint8_t *d_k2,
                        uint8_t *d_hash, uint8_t *d_rs, void *stream);
 
+/* ---- device-resident CipherState tables ---------------------------------
+ * A Noise CipherState is the pair (k, n).  A table holds nsess of them in HBM
+ * (32-byte key rows and 64-bit counters) and assigns the nonces of a batch on
+ * the GPU, so handshake -> split -> transport runs without per-record host
+ * work and with no nonce state on the host.
+ *
+ * Assignment rule: exactly what nrec consecutive calls on a host CipherState
+ * would do (noise.cpp:393-427).  For a session s with counter n0 at entry and
+ * c records in the batch, a record's rank r is the number of earlier records
+ * of s in the batch (record order), and room = (2^64-2 - n0) mod 2^64:
+ *  - r < room: accepted, nonce (n0 + r) mod 2^64 (for n0 = 2^64-1 the
+ *    reference's n++ wraps, and so does this: 2^64-1, 0, 1, ...);
+ *  - r >= room: refused (n == 2^64-2, noise.cpp:398-400, 416-418): status
+ *    NOISE_GPU_REC_NONCE, the record is not processed, nothing is written to
+ *    its output, its nonce field is unspecified;
+ *  - the counter ends at n0 + min(c, room).  Decrypt advances it for accepted
+ *    records whatever their tag does (noise.cpp:421).
+ * A keyless session (all-zero row, e.g. a failed handshake's split row): its
+ * records get NOISE_GPU_REC_BAD_KEY, are not processed, and the counter stays
+ * (noise.cpp:395, 413).  A session index >= nsess gets NOISE_GPU_REC_BAD_KEY
+ * and touches no table memory.  The assignment is deterministic (a stable
+ * sort of the batch by session, no atomics): a peer table fed the same wire
+ * order assigns the same nonces.
+ *
+ * Contract: a table lives on the device current at create and is used by ONE
+ * stream at a time.  Calls on one stream need no synchronisation between them
+ * (two back-to-back batches see each other's counters); before using the
+ * table on another stream, synchronise the first.  Scratch (the sort's tables
+ * and private index / nonce / descriptor copies) belongs to the table and
+ * only grows; a smaller one is zeroed and freed stream-ordered.
+ * noise_gpu_cs_destroy zeroes keys, counters and scratch before it frees
+ * them (it synchronises the device). */
+typedef struct noise_gpu_cs noise_gpu_cs;
+#define NOISE_GPU_REC_NONCE 3u /* record refused: its session's n == 2^64-2 */
+
+/* 1 <= nsess <= 2^32-2; every row keyless, every n = 0 */
+int noise_gpu_cs_create(uint64_t nsess, noise_gpu_cs **out);
+/* wipes keys, counters and scratch, then frees; NULL is OK */
+int noise_gpu_cs_destroy(noise_gpu_cs *cs);
+/* InitializeKey(k) for sessions [first, first + count): rows copied from
+ * d_keys (32-byte rows at key_stride >= 32; what noise_gpu_hs_split wrote is
+ * accepted as is, an all-zero row = keyless); n <- d_n[j], or 0 when d_n is
+ * NULL.  d_keys == NULL with d_n given keeps the keys and sets the counters
+ * only (set_nonce). */
+int noise_gpu_cs_set(noise_gpu_cs *cs, uint64_t first, uint64_t count,
+                     const uint8_t *d_keys, uint64_t key_stride, const uint64_t *d_n,
+                     void *stream);
+/* copy out rows (packed, 32 bytes each) and / or counters of [first, first +
+ * count); either pointer may be NULL.  Migration to a host CipherState. */
+int noise_gpu_cs_get(const noise_gpu_cs *cs, uint64_t first, uint64_t count,
+                     uint8_t *d_keys, uint64_t *d_n, void *stream);
+/* REKEY (noise.cpp:429-439) of the sessions d_sess[0..count) (each at most
+ * once), or of all when d_sess == NULL; n untouched; a keyless row stays
+ * keyless; an index >= nsess is skipped. */
+int noise_gpu_cs_rekey(noise_gpu_cs *cs, const uint32_t *d_sess, uint64_t count, void *stream);
+/* The primitive.  Record i belongs to session *(uint32_t *)(d_sess + i *
+ * sess_stride); its nonce is written to *(uint64_t *)(d_nonce + i *
+ * nonce_stride).  Strides 4 / 8 address plain arrays; stride
+ * sizeof(noise_gpu_record) with the addresses of recs[0].key_idx /
+ * recs[0].nonce a descriptor array (strides are multiples of 4 / 8, the arrays
+ * aligned to match).  d_status (may be NULL) receives NOISE_GPU_REC_OK /
+ * _BAD_KEY / _NONCE per record.  Afterwards every session's n has advanced by
+ * its number of accepted records.  nrec <= 2^31. */
+int noise_gpu_cs_assign(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t sess_stride,
+                        uint8_t *d_nonce, uint64_t nonce_stride, uint8_t *d_status,
+                        uint64_t nrec, void *stream);
+/* assign + noise_gpu_{en,de}crypt_records_sized over the table's key rows,
+ * stream-ordered, no host synchronisation.  key_idx is the session; the
+ * descriptors' nonce fields are filled (d_recs is in/out).  d_status: as
+ * noise_gpu_cs_assign for encrypt (may be NULL); decrypt (required) adds
+ * NOISE_GPU_REC_BAD_MAC. */
+int noise_gpu_cs_encrypt_records(noise_gpu_cs *cs, noise_gpu_record *d_recs, uint64_t nrec,
+                                 const uint8_t *d_in, uint8_t *d_out, const uint8_t *d_ad,
+                                 uint8_t *d_status, uint64_t len_sum, void *stream);
+int noise_gpu_cs_decrypt_records(noise_gpu_cs *cs, noise_gpu_record *d_recs, uint64_t nrec,
+                                 const uint8_t *d_in, uint8_t *d_out, const uint8_t *d_ad,
+                                 uint8_t *d_status, uint64_t len_sum, void *stream);
+/* assign + noise_gpu_{en,de}crypt_sessions (same shapes; NOISE_GPU_E_ARG
+ * otherwise): record i belongs to session d_sess[i]. */
+int noise_gpu_cs_encrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess, const uint8_t *d_in,
+                                  uint64_t in_stride, uint8_t *d_out, uint64_t out_stride,
+                                  uint32_t len, uint8_t *d_status, uint64_t nrec, void *stream);
+int noise_gpu_cs_decrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess, const uint8_t *d_in,
+                                  uint64_t in_stride, uint8_t *d_out, uint64_t out_stride,
+                                  uint32_t len, uint8_t *d_status, uint64_t nrec, void *stream);
+
 /* ---- host-buffer entry points (synchronous) ----------------------------
  * Used by the CipherState shim for single records (encrypt_with_ad /
  * decrypt_with_ad / rekey).  A record of <= 65535 bytes with <= 8192 bytes of

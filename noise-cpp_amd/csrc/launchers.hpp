@@ -189,6 +189,43 @@ hipError_t launch_hs_split(HsSession *S, uint64_t n, uint8_t *k1, uint8_t *k2, u
 hipError_t launch_hs_status(const HsSession *S, uint64_t n, uint8_t *out, hipStream_t st);
 hipError_t launch_hs_wipe(HsSession *S, uint64_t n, hipStream_t st);
 
+// ---- device-resident CipherState tables (cstate_kernels.hip) ------------
+struct CsTableView {
+  uint8_t *keys;    // [nsess][32]
+  uint64_t *ctr;    // [nsess] the counters n
+  uint32_t *start;  // [nsess] rank scratch: where a session's run starts in the sorted batch
+  uint32_t nsess;
+};
+// One batch: record i belongs to session *(uint32_t *)(sess + i * sess_stride).
+// An accepted record's nonce goes to nonce + i * nonce_stride (and to nonce2,
+// if given); a refused one sets the uint32 at kill + i * kill_stride (if
+// given) to 0xffffffff; status (if given) receives NOISE_GPU_REC_*.
+struct CsAssign {
+  const uint8_t *sess;
+  uint64_t sess_stride;
+  uint8_t *nonce;
+  uint64_t nonce_stride;
+  uint8_t *nonce2;
+  uint64_t nonce2_stride;
+  uint8_t *kill;
+  uint64_t kill_stride;
+  uint8_t *status;
+  uint64_t nrec;  // < 2^31
+};
+// bytes of scratch launch_cs_assign needs for nrec records (0: none)
+size_t cs_assign_scratch_bytes(uint64_t nrec);
+hipError_t launch_cs_assign(const CsTableView &t, const CsAssign &a, void *scratch,
+                            hipStream_t stream);
+// status[i] = NOISE_GPU_REC_NONCE where the private index differs from the caller's
+hipError_t launch_cs_fix(const uint8_t *sess, uint64_t sess_stride, const uint8_t *kill,
+                         uint64_t kill_stride, uint8_t *status, uint64_t nrec, hipStream_t stream);
+// rows (src, may be null: keys kept) and counters (n, null: 0) of [first, first + count)
+hipError_t launch_cs_set(const CsTableView &t, uint64_t first, uint64_t count, const uint8_t *src,
+                         uint64_t stride, const uint64_t *n, hipStream_t stream);
+// REKEY of sess[0..count), or of sessions [0, count) when sess is null
+hipError_t launch_cs_rekey(const CsTableView &t, const uint32_t *sess, uint64_t count,
+                           hipStream_t stream);
+
 // C-ABI helpers shared by the API translation units (noise_gpu_api.hip)
 int api_hip_fail(hipError_t e, const char *what);
 int api_arg_fail(const char *msg);

@@ -789,6 +789,246 @@ int noise_gpu_rekey_keys(uint8_t *d_keys, uint64_t nkeys, void *stream) {
   return NOISE_GPU_OK;
 }
 
+// ---- device-resident CipherState tables ------------------------------------
+}  // extern "C"
+
+// nsess x (key row, counter n, rank scratch) and the batch scratch, in HBM on
+// the device current at create
+struct noise_gpu_cs {
+  noise_amd::CsTableView t{};
+  void *scratch = nullptr;  // grow-only; the sort's tables and the private index / nonce copies
+  size_t scratch_size = 0;
+};
+
+namespace {
+
+constexpr uint64_t kCsMaxSess = 0xfffffffeull;  // 2^32-2: 0xffffffff marks a refused record
+constexpr uint64_t kCsMaxRec = 1ull << 31;
+
+// the table's scratch, >= bytes; the smaller one is wiped and freed
+// stream-ordered after the launches that still use it
+hipError_t cs_scratch(noise_gpu_cs *cs, size_t bytes, hipStream_t st) {
+  if (bytes <= cs->scratch_size) return hipSuccess;
+  hipError_t e = noise_amd::dev_wipe_free(cs->scratch, cs->scratch_size, st);
+  cs->scratch = nullptr;
+  cs->scratch_size = 0;
+  if (e != hipSuccess) return e;
+  if ((e = noise_amd::dev_alloc(&cs->scratch, bytes, st)) != hipSuccess) return e;
+  cs->scratch_size = bytes;
+  return hipSuccess;
+}
+
+int cs_check_range(const noise_gpu_cs *cs, uint64_t first, uint64_t count) {
+  if (first + count < first) return arg_fail("first + count overflows");
+  if (!cs) return arg_fail("null table");
+  if (first + count > cs->t.nsess) return arg_fail("sessions [first, first + count) outside the table");
+  return NOISE_GPU_OK;
+}
+
+int cs_check_assign(const noise_gpu_cs *cs, const void *d_sess, uint64_t sess_stride,
+                    const void *d_nonce, uint64_t nonce_stride, uint64_t nrec) {
+  if (sess_stride == 0 || (sess_stride & 3u)) return arg_fail("session stride must be a non-zero multiple of 4");
+  if (nonce_stride == 0 || (nonce_stride & 7u)) return arg_fail("nonce stride must be a non-zero multiple of 8");
+  if (nrec > kCsMaxRec) return arg_fail("more than 2^31 records in one batch");
+  if (!cs) return arg_fail("null table");
+  if (nrec == 0) return NOISE_GPU_OK;
+  if (!d_sess || !d_nonce) return arg_fail("null session / nonce array");
+  if ((reinterpret_cast<uintptr_t>(d_sess) & 3u) || (reinterpret_cast<uintptr_t>(d_nonce) & 7u))
+    return arg_fail("session / nonce arrays must be 4 / 8-byte aligned");
+  return NOISE_GPU_OK;
+}
+
+int cs_records(bool decrypt, noise_gpu_cs *cs, noise_gpu_record *d_recs, uint64_t nrec,
+               const uint8_t *d_in, uint8_t *d_out, const uint8_t *d_ad, uint8_t *d_status,
+               uint64_t len_sum, void *stream) {
+  if (nrec > kCsMaxRec) return arg_fail("more than 2^31 records in one batch");
+  if (!cs) return arg_fail("null table");
+  if (nrec == 0) return NOISE_GPU_OK;
+  if (!d_recs || !d_in || !d_out || (decrypt && !d_status))
+    return arg_fail(decrypt ? "null descriptors / buffers / status" : "null descriptors / buffers");
+  if (reinterpret_cast<uintptr_t>(d_recs) & 7u) return arg_fail("descriptors must be 8-byte aligned");
+  int rc = check_device();
+  if (rc) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  // scratch: the sort's tables | a private copy of the descriptors, in which
+  // a refused record's key_idx is out of range for the AEAD kernels
+  const size_t sort_bytes = align16(noise_amd::cs_assign_scratch_bytes(nrec));
+  HIP_TRY(cs_scratch(cs, sort_bytes + nrec * sizeof(noise_gpu_record), st));
+  uint8_t *base = static_cast<uint8_t *>(cs->scratch);
+  noise_gpu_record *priv = reinterpret_cast<noise_gpu_record *>(base + sort_bytes);
+  HIP_TRY(hipMemcpyAsync(priv, d_recs, nrec * sizeof(noise_gpu_record), hipMemcpyDeviceToDevice, st));
+  constexpr uint64_t kRec = sizeof(noise_gpu_record);
+  uint8_t *caller = reinterpret_cast<uint8_t *>(d_recs), *mine = reinterpret_cast<uint8_t *>(priv);
+  const noise_amd::CsAssign a{caller + offsetof(noise_gpu_record, key_idx), kRec,
+                              caller + offsetof(noise_gpu_record, nonce), kRec,
+                              mine + offsetof(noise_gpu_record, nonce), kRec,
+                              mine + offsetof(noise_gpu_record, key_idx), kRec,
+                              decrypt ? nullptr : d_status, nrec};
+  HIP_TRY(noise_amd::launch_cs_assign(cs->t, a, base, st));
+  HIP_TRY(noise_amd::launch_aead_records(decrypt, cs->t.keys, cs->t.nsess, priv, nrec, d_in, d_out,
+                                         d_ad, decrypt ? d_status : nullptr, st, len_sum));
+  if (decrypt)
+    HIP_TRY(noise_amd::launch_cs_fix(a.sess, kRec, a.kill, kRec, d_status, nrec, st));
+  return NOISE_GPU_OK;
+}
+
+int cs_sessions(bool decrypt, noise_gpu_cs *cs, const uint32_t *d_sess, const uint8_t *d_in,
+                uint64_t in_stride, uint8_t *d_out, uint64_t out_stride, uint32_t len,
+                uint8_t *d_status, uint64_t nrec, void *stream) {
+  if (nrec > kCsMaxRec) return arg_fail("more than 2^31 records in one batch");
+  if (!cs) return arg_fail("null table");
+  if (nrec == 0) return NOISE_GPU_OK;
+  if (!d_sess || (reinterpret_cast<uintptr_t>(d_sess) & 3u))
+    return arg_fail("null or unaligned session array");
+  int rc = check_uniform(decrypt, d_in, in_stride, d_out, out_stride, len, nullptr, 0, d_status, nrec);
+  if (rc) return rc;
+  if (!noise_amd::sessions_supported(len, d_in, in_stride, d_out, out_stride))
+    return arg_fail("sessions batches need a tile length and 16-byte aligned buffers/strides "
+                    "(see noise_gpu_encrypt_sessions)");
+  if ((rc = check_device())) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  // scratch: the sort's tables | the nonces | a private copy of the index, in
+  // which a refused record carries an out-of-range value
+  const size_t sort_bytes = align16(noise_amd::cs_assign_scratch_bytes(nrec));
+  HIP_TRY(cs_scratch(cs, sort_bytes + 12 * nrec, st));
+  uint8_t *base = static_cast<uint8_t *>(cs->scratch);
+  uint8_t *nonces = base + sort_bytes, *idx = nonces + 8 * nrec;
+  HIP_TRY(hipMemcpyAsync(idx, d_sess, 4 * nrec, hipMemcpyDeviceToDevice, st));
+  const uint8_t *sess = reinterpret_cast<const uint8_t *>(d_sess);
+  const noise_amd::CsAssign a{sess, 4, nonces, 8, nullptr, 0, idx, 4, decrypt ? nullptr : d_status, nrec};
+  HIP_TRY(noise_amd::launch_cs_assign(cs->t, a, base, st));
+  HIP_TRY(noise_amd::launch_aead_sessions(decrypt, cs->t.keys, cs->t.nsess,
+                                          reinterpret_cast<const uint32_t *>(idx),
+                                          reinterpret_cast<const uint64_t *>(nonces), d_in, in_stride,
+                                          d_out, out_stride, len, decrypt ? d_status : nullptr, nrec, st));
+  if (decrypt) HIP_TRY(noise_amd::launch_cs_fix(sess, 4, idx, 4, d_status, nrec, st));
+  return NOISE_GPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int noise_gpu_cs_create(uint64_t nsess, noise_gpu_cs **out) {
+  if (!out) return arg_fail("null output");
+  *out = nullptr;
+  if (nsess == 0 || nsess > kCsMaxSess) return arg_fail("a CipherState table holds 1 .. 2^32-2 sessions");
+  int rc = check_device();
+  if (rc) return rc;
+  noise_gpu_cs *cs = new (std::nothrow) noise_gpu_cs();
+  if (!cs) return arg_fail("out of host memory");
+  cs->t.nsess = (uint32_t)nsess;
+  hipError_t e = hipMalloc(&cs->t.keys, nsess * 32);
+  if (e == hipSuccess) e = hipMalloc(&cs->t.ctr, nsess * 8);
+  if (e == hipSuccess) e = hipMalloc(&cs->t.start, nsess * 4);
+  if (e == hipSuccess) e = hipMemset(cs->t.keys, 0, nsess * 32);
+  if (e == hipSuccess) e = hipMemset(cs->t.ctr, 0, nsess * 8);
+  if (e == hipSuccess) e = hipMemset(cs->t.start, 0, nsess * 4);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    if (cs->t.keys) (void)hipFree(cs->t.keys);
+    if (cs->t.ctr) (void)hipFree(cs->t.ctr);
+    if (cs->t.start) (void)hipFree(cs->t.start);
+    delete cs;
+    return hip_fail(e, "CipherState table allocation");
+  }
+  *out = cs;
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cs_destroy(noise_gpu_cs *cs) {
+  if (!cs) return NOISE_GPU_OK;
+  int rc = NOISE_GPU_OK;
+  auto keep = [&rc](hipError_t e) {
+    if (e != hipSuccess) rc = hip_fail(e, "noise_gpu_cs_destroy");
+  };
+  keep(hipDeviceSynchronize());  // the table's last calls, whatever stream they ran on
+  const uint64_t n = cs->t.nsess;
+  keep(hipMemset(cs->t.keys, 0, n * 32));
+  keep(hipMemset(cs->t.ctr, 0, n * 8));
+  keep(hipMemset(cs->t.start, 0, n * 4));
+  keep(noise_amd::dev_wipe_free(cs->scratch, cs->scratch_size, nullptr));
+  keep(hipDeviceSynchronize());
+  (void)hipFree(cs->t.keys);
+  (void)hipFree(cs->t.ctr);
+  (void)hipFree(cs->t.start);
+  delete cs;
+  return rc;
+}
+
+int noise_gpu_cs_set(noise_gpu_cs *cs, uint64_t first, uint64_t count, const uint8_t *d_keys,
+                     uint64_t key_stride, const uint64_t *d_n, void *stream) {
+  if (d_keys && key_stride < 32) return arg_fail("key rows are 32 bytes: key_stride >= 32");
+  if (reinterpret_cast<uintptr_t>(d_n) & 7u) return arg_fail("counters must be 8-byte aligned");
+  int rc = cs_check_range(cs, first, count);
+  if (rc || count == 0) return rc;
+  if (!d_keys && !d_n) return arg_fail("neither key rows nor counters given");
+  if ((rc = check_device())) return rc;
+  HIP_TRY(noise_amd::launch_cs_set(cs->t, first, count, d_keys, key_stride, d_n, (hipStream_t)stream));
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cs_get(const noise_gpu_cs *cs, uint64_t first, uint64_t count, uint8_t *d_keys,
+                     uint64_t *d_n, void *stream) {
+  int rc = cs_check_range(cs, first, count);
+  if (rc || count == 0) return rc;
+  if ((rc = check_device())) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  if (d_keys)
+    HIP_TRY(hipMemcpyAsync(d_keys, cs->t.keys + 32 * first, 32 * count, hipMemcpyDeviceToDevice, st));
+  if (d_n) HIP_TRY(hipMemcpyAsync(d_n, cs->t.ctr + first, 8 * count, hipMemcpyDeviceToDevice, st));
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cs_rekey(noise_gpu_cs *cs, const uint32_t *d_sess, uint64_t count, void *stream) {
+  if (reinterpret_cast<uintptr_t>(d_sess) & 3u) return arg_fail("session array must be 4-byte aligned");
+  if (!cs) return arg_fail("null table");
+  if (!d_sess) count = cs->t.nsess;
+  if (count == 0) return NOISE_GPU_OK;
+  int rc = check_device();
+  if (rc) return rc;
+  HIP_TRY(noise_amd::launch_cs_rekey(cs->t, d_sess, count, (hipStream_t)stream));
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cs_assign(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t sess_stride,
+                        uint8_t *d_nonce, uint64_t nonce_stride, uint8_t *d_status, uint64_t nrec,
+                        void *stream) {
+  int rc = cs_check_assign(cs, d_sess, sess_stride, d_nonce, nonce_stride, nrec);
+  if (rc || nrec == 0) return rc;
+  if ((rc = check_device())) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(cs_scratch(cs, noise_amd::cs_assign_scratch_bytes(nrec), st));
+  const noise_amd::CsAssign a{d_sess, sess_stride, d_nonce, nonce_stride, nullptr, 0,
+                              nullptr, 0, d_status, nrec};
+  HIP_TRY(noise_amd::launch_cs_assign(cs->t, a, cs->scratch, st));
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cs_encrypt_records(noise_gpu_cs *cs, noise_gpu_record *d_recs, uint64_t nrec,
+                                 const uint8_t *d_in, uint8_t *d_out, const uint8_t *d_ad,
+                                 uint8_t *d_status, uint64_t len_sum, void *stream) {
+  return cs_records(false, cs, d_recs, nrec, d_in, d_out, d_ad, d_status, len_sum, stream);
+}
+
+int noise_gpu_cs_decrypt_records(noise_gpu_cs *cs, noise_gpu_record *d_recs, uint64_t nrec,
+                                 const uint8_t *d_in, uint8_t *d_out, const uint8_t *d_ad,
+                                 uint8_t *d_status, uint64_t len_sum, void *stream) {
+  return cs_records(true, cs, d_recs, nrec, d_in, d_out, d_ad, d_status, len_sum, stream);
+}
+
+int noise_gpu_cs_encrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess, const uint8_t *d_in,
+                                  uint64_t in_stride, uint8_t *d_out, uint64_t out_stride,
+                                  uint32_t len, uint8_t *d_status, uint64_t nrec, void *stream) {
+  return cs_sessions(false, cs, d_sess, d_in, in_stride, d_out, out_stride, len, d_status, nrec, stream);
+}
+
+int noise_gpu_cs_decrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess, const uint8_t *d_in,
+                                  uint64_t in_stride, uint8_t *d_out, uint64_t out_stride,
+                                  uint32_t len, uint8_t *d_status, uint64_t nrec, void *stream) {
+  return cs_sessions(true, cs, d_sess, d_in, in_stride, d_out, out_stride, len, d_status, nrec, stream);
+}
+
 int noise_gpu_x25519(const uint8_t *d_scalars, const uint8_t *d_points,
                      uint8_t *d_out, uint64_t n, void *stream) {
   if (n == 0) return NOISE_GPU_OK;

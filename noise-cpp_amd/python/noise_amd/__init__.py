@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("NOISE_AMD_LIB") or os.path.join(PKG, "lib", "libnoise
 HEADER = os.path.join(ROOT, "include", "noise_gpu.h")
 
 OK, E_NONCE, E_MAC, E_ARG, E_HIP, E_NODEV = 0, 1, 2, 3, 4, 5
-REC_OK, REC_BAD_MAC, REC_BAD_KEY = 0, 1, 2
+REC_OK, REC_BAD_MAC, REC_BAD_KEY, REC_NONCE = 0, 1, 2, 3
 NONCE_LIMIT = (1 << 64) - 2  # noise.cpp:398 refuses n == 2^64-2
 
 
@@ -154,6 +154,18 @@ def load(path=LIB_PATH):
                                                      u8p, u8p, vp]),
         "noise_gpu_hs_status": (ctypes.c_int, [vp, u8p, vp]),
         "noise_gpu_hs_split": (ctypes.c_int, [vp, u8p, u8p, u8p, u8p, vp]),
+        "noise_gpu_cs_create": (ctypes.c_int, [u64, ctypes.POINTER(ctypes.c_void_p)]),
+        "noise_gpu_cs_destroy": (ctypes.c_int, [vp]),
+        "noise_gpu_cs_set": (ctypes.c_int, [vp, u64, u64, u8p, u64, u8p, vp]),
+        "noise_gpu_cs_get": (ctypes.c_int, [vp, u64, u64, u8p, u8p, vp]),
+        "noise_gpu_cs_rekey": (ctypes.c_int, [vp, u8p, u64, vp]),
+        "noise_gpu_cs_assign": (ctypes.c_int, [vp, u8p, u64, u8p, u64, u8p, u64, vp]),
+        "noise_gpu_cs_encrypt_records": (ctypes.c_int, [vp, u8p, u64, u8p, u8p, u8p, u8p, u64, vp]),
+        "noise_gpu_cs_decrypt_records": (ctypes.c_int, [vp, u8p, u64, u8p, u8p, u8p, u8p, u64, vp]),
+        "noise_gpu_cs_encrypt_sessions": (ctypes.c_int, [vp, u8p, u8p, u64, u8p, u64, u32, u8p, u64,
+                                                         vp]),
+        "noise_gpu_cs_decrypt_sessions": (ctypes.c_int, [vp, u8p, u8p, u64, u8p, u64, u32, u8p, u64,
+                                                         vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -314,6 +326,79 @@ class HandshakeBatch:
     def split(self, d_k1, d_k2, d_hash=None, d_rs=None, stream=None):
         _check(self.lib.noise_gpu_hs_split(self.h, _ptr(d_k1), _ptr(d_k2), _ptr(d_hash), _ptr(d_rs),
                                            _stream(stream)), "noise_gpu_hs_split")
+
+
+class CipherStateTable:
+    """nsess device-resident CipherStates (noise_gpu_cs_*): key rows and
+    counters in HBM, nonces assigned on the GPU in the batch's record order.
+    One stream at a time; tensors are HBM allocations (uint8 unless noted)."""
+
+    RECORD_KEY_IDX_OFF, RECORD_NONCE_OFF = Record.key_idx.offset, Record.nonce.offset
+
+    def __init__(self, nsess):
+        self.lib, self.nsess = load(), nsess
+        h = ctypes.c_void_p()
+        _check(self.lib.noise_gpu_cs_create(nsess, ctypes.byref(h)), "noise_gpu_cs_create")
+        self.h = h
+
+    def close(self):
+        if self.h:
+            _check(self.lib.noise_gpu_cs_destroy(self.h), "noise_gpu_cs_destroy")
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set(self, first, count, d_keys, key_stride=32, d_n=None, stream=None):
+        """d_keys: count key rows at key_stride (None: keep the keys); d_n:
+        int64 tensor of count counters (None: 0)."""
+        _check(self.lib.noise_gpu_cs_set(self.h, first, count, _ptr(d_keys), key_stride, _ptr(d_n),
+                                         _stream(stream)), "noise_gpu_cs_set")
+
+    def get(self, first, count, d_keys=None, d_n=None, stream=None):
+        _check(self.lib.noise_gpu_cs_get(self.h, first, count, _ptr(d_keys), _ptr(d_n),
+                                         _stream(stream)), "noise_gpu_cs_get")
+
+    def rekey(self, d_sess=None, count=0, stream=None):
+        """d_sess: int32 tensor of count session indices, or None: all."""
+        _check(self.lib.noise_gpu_cs_rekey(self.h, _ptr(d_sess), count, _stream(stream)),
+               "noise_gpu_cs_rekey")
+
+    def assign(self, d_sess, d_nonce, nrec, d_status=None, sess_stride=4, nonce_stride=8,
+               sess_offset=0, nonce_offset=0, stream=None):
+        """Plain arrays (int32 sessions, int64 nonces) by default; for a
+        descriptor array pass it as both d_sess and d_nonce with strides 48 and
+        the offsets RECORD_KEY_IDX_OFF / RECORD_NONCE_OFF."""
+        _check(self.lib.noise_gpu_cs_assign(
+            self.h, ctypes.c_void_p(d_sess.data_ptr() + sess_offset), sess_stride,
+            ctypes.c_void_p(d_nonce.data_ptr() + nonce_offset), nonce_stride, _ptr(d_status), nrec,
+            _stream(stream)), "noise_gpu_cs_assign")
+
+    def encrypt_records(self, d_recs, nrec, d_in, d_out, d_ad=None, d_status=None, len_sum=0,
+                        stream=None):
+        _check(self.lib.noise_gpu_cs_encrypt_records(
+            self.h, _ptr(d_recs), nrec, _ptr(d_in), _ptr(d_out), _ptr(d_ad), _ptr(d_status), len_sum,
+            _stream(stream)), "noise_gpu_cs_encrypt_records")
+
+    def decrypt_records(self, d_recs, nrec, d_in, d_out, d_status, d_ad=None, len_sum=0, stream=None):
+        _check(self.lib.noise_gpu_cs_decrypt_records(
+            self.h, _ptr(d_recs), nrec, _ptr(d_in), _ptr(d_out), _ptr(d_ad), _ptr(d_status), len_sum,
+            _stream(stream)), "noise_gpu_cs_decrypt_records")
+
+    def encrypt_sessions(self, d_sess, d_in, in_stride, d_out, out_stride, length, nrec,
+                         d_status=None, stream=None):
+        _check(self.lib.noise_gpu_cs_encrypt_sessions(
+            self.h, _ptr(d_sess), _ptr(d_in), in_stride, _ptr(d_out), out_stride, length,
+            _ptr(d_status), nrec, _stream(stream)), "noise_gpu_cs_encrypt_sessions")
+
+    def decrypt_sessions(self, d_sess, d_in, in_stride, d_out, out_stride, length, d_status, nrec,
+                         stream=None):
+        _check(self.lib.noise_gpu_cs_decrypt_sessions(
+            self.h, _ptr(d_sess), _ptr(d_in), in_stride, _ptr(d_out), out_stride, length,
+            _ptr(d_status), nrec, _stream(stream)), "noise_gpu_cs_decrypt_sessions")
 
 
 # ---- host-buffer entry points (CipherState single-record path) ------------
