@@ -166,17 +166,29 @@ constexpr uint64_t kStageBytes = NOISE_STAGE_BYTES;
 #define NOISE_UNIFORM_SPAN 256
 #endif
 
-// the LDS-staged tile kernel: aligned, AD-free records of an exact length
-static hipError_t launch_uniform_exact(bool decrypt, const TileArgs &ta, uint32_t len, bool contig,
+// the LDS-staged tile kernel: aligned, AD-free records of an exact length.
+// One launch per run of nonces that share their high word (the kernel starts
+// every ChaCha block from round-1 columns computed here for that word): a
+// second one only where the batch crosses a multiple of 2^32.
+static hipError_t launch_uniform_exact(bool decrypt, const TileArgs &b, uint32_t len, bool contig,
                                        hipStream_t stream) {
-  for_exact_len(len, [&](auto L) {
-    for_bools(decrypt, contig, [&](auto DEC, auto CONTIG) {
-      constexpr int LEN = decltype(L)::value;
-      hipLaunchKernelGGL((k_aead_tile<decltype(DEC)::value, LEN, decltype(CONTIG)::value, kTileUniform, 0, 1,
-                                      (LEN >= 256 && LEN <= 8192) ? NOISE_UNIFORM_SPAN : 256>),
-                         tile_grid(ta.nrec), dim3(64), 0, stream, ta);
+  for (uint64_t r0 = 0; r0 < b.nrec;) {
+    TileArgs ta = b;
+    tile_set_uniform(ta, b.key, b.nonce0 + r0);
+    ta.nrec = uniform_run_len(ta.nonce0, b.nrec - r0);
+    ta.in = b.in + r0 * b.in_stride;
+    ta.out = b.out + r0 * b.out_stride;
+    if (b.status) ta.status = b.status + r0;
+    for_exact_len(len, [&](auto L) {
+      for_bools(decrypt, contig, [&](auto DEC, auto CONTIG) {
+        constexpr int LEN = decltype(L)::value;
+        hipLaunchKernelGGL((k_aead_tile<decltype(DEC)::value, LEN, decltype(CONTIG)::value, kTileUniform, 0, 1,
+                                        (LEN >= 256 && LEN <= 8192) ? NOISE_UNIFORM_SPAN : 256>),
+                           tile_grid(ta.nrec), dim3(64), 0, stream, ta);
+      });
     });
-  });
+    r0 += ta.nrec;
+  }
   return hipGetLastError();
 }
 
@@ -191,7 +203,7 @@ static hipError_t launch_uniform_masked(bool decrypt, TileArgs ta, uint32_t len,
       constexpr int CAP = decltype(L)::value;
       constexpr uint64_t rps = MTileCfg<CAP>::RPS;
       hipLaunchKernelGGL((k_aead_mtile<decltype(DEC)::value, CAP, kMTUniform>),
-                         dim3((unsigned)((ta.nrec + rps - 1) / rps)), dim3(64), 0, stream, ta);
+                         dim3(capped((ta.nrec + rps - 1) / rps, NOISE_GRID_CAP)), dim3(64), 0, stream, ta);
     });
   });
   return hipGetLastError();

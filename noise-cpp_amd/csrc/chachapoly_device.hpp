@@ -144,6 +144,24 @@ __device__ __forceinline__ ChaPre chacha_pre(const uint32_t k[8], uint32_t n_lo,
   return p;
 }
 
+// One key for the whole launch and a nonce range inside one 2^32 block:
+// columns 1 (key only) and 3 (key, n_hi) after round 1 are the same for every
+// record, so the host computes them once (tile_launch.hpp, uniform_round1) and
+// a lane runs column 2 alone.
+struct ChaUniform {
+  uint32_t c1[4], c3[4];  // x1 x5 x9 x13, x3 x7 x11 x15 after round 1's column step
+};
+
+__device__ __forceinline__ ChaPre chacha_pre_uniform(const uint32_t k[8], uint32_t n_lo,
+                                                     const ChaUniform &u) {
+  ChaPre p;
+  p.x1 = u.c1[0]; p.x5 = u.c1[1]; p.x9 = u.c1[2]; p.x13 = u.c1[3];
+  p.x2 = kSigma2; p.x6 = k[2]; p.x10 = k[6]; p.x14 = n_lo;
+  p.x3 = u.c3[0]; p.x7 = u.c3[1]; p.x11 = u.c3[2]; p.x15 = u.c3[3];
+  NOISE_QR(p.x2, p.x6, p.x10, p.x14)
+  return p;
+}
+
 __device__ __forceinline__ void chacha20_block_pre(const uint32_t k[8],
                                                    uint32_t ctr,
                                                    const ChaPre &pre,

@@ -95,14 +95,7 @@ constexpr uint64_t kClassifyAvgLen = 2048;  // below kClassifyMin: classify when
 #define NOISE_SEG_CAP (1ull << 24)
 #endif
 constexpr uint64_t kSegCapMax = NOISE_SEG_CAP;  // 16 Mi segments = 16 GiB per call
-// Grid cap of the per-class launches, whose sizes are known only on the
-// device (capped grids stride over their work).  8192 single-wave workgroups
-// = 4x what the LDS budget keeps resident (8 per CU): the dispatcher refills
-// CUs as workgroups finish, which balanced config 4 best (2048: -6 %, 16384
-// and uncapped: -3 %, MI355X).  Overridable for the CPU emulation build.
-#ifndef NOISE_GRID_CAP
-#define NOISE_GRID_CAP 8192u
-#endif
+// (the grid cap of the per-class launches, NOISE_GRID_CAP: tile_launch.hpp)
 
 // an all-zero key row is "no key" (Noise HasKey() false, e.g. the rows
 // noise_gpu_hs_split leaves for failed handshakes): never used to encrypt
@@ -649,10 +642,6 @@ __global__ __launch_bounds__(kGenBlock) void k_aead_records(
 }
 
 static inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
-static inline unsigned capped(uint64_t want, uint64_t cap) {
-  if (want == 0) want = 1;
-  return (unsigned)(want < cap ? want : cap);
-}
 
 // one records call: the arguments of launch_aead_records
 struct RecCall {

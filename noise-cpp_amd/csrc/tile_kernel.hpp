@@ -17,8 +17,9 @@
 //     G tiles per super-tile.  Lane j of a record owns the contiguous
 //     256-byte span [256j, 256j+256): 4 ChaCha blocks (counters 1+4j..4+4j)
 //     and 16 Poly1305 blocks, Horner-evaluated with the clamped r;
-//   * the G partial sums recombine as  sum_j acc_j * r^(16(G-1-j)),
-//     log2(G) general products per lane + a log2(G)-step butterfly.
+//   * the G partial sums recombine as  sum_j acc_j * r^(16(G-1-j)): one
+//     general product per lane for G <= 4 (the key lane hands out r^16, r^32,
+//     r^48), log2(G) of them for wider records, + a log2(G)-step butterfly.
 // Per tile the wave does: compute (LDS in place) -> gather the output
 // records into VGPRs -> issue the NEXT tile's LDS-DMA and THIS tile's global
 // stores back to back, so the two memory round trips overlap; the only
@@ -140,7 +141,7 @@ struct SegPartial {              // P_s in radix 2^32: words h0..h3 (h4, small,
 
 struct TileArgs {
   KeyArg key;         // kTileUniform
-  uint64_t nonce0;    // kTileUniform
+  uint64_t nonce0;    // kTileUniform: nonce0 .. nonce0 + nrec - 1 share their high word
   const uint8_t *in;
   uint64_t in_stride;  // kTileUniform / kTileSessions
   uint8_t *out;
@@ -171,6 +172,9 @@ struct TileArgs {
   const unsigned long long *ntails;     // kMTTail*: their count (device)
   const unsigned long long *tail_split; // kMTTail*: chunk boundaries in tails (device), or null
   const unsigned long long *nlong;      // kMTTail*: long records in the scratch (device)
+  // kTileUniform: round-1 columns of (key, nonce0 >> 32) (tile_launch.hpp).  Last, so
+  // that the other fields keep their kernel-argument offsets.
+  ChaUniform uni;
 };
 
 // kTileSeg*: all segments, or chunk a.chunk of them
@@ -340,6 +344,10 @@ template <bool DECRYPT, int L, bool CONTIG, int MODE = kTileUniform, int ABL = 0
 __global__ __launch_bounds__(64) void k_aead_tile(const TileArgs a) {
   using C = TileCfg<L, SPAN>;
   constexpr bool KEYED = MODE != kTileUniform;
+  // uniform: start the ChaCha blocks from a.uni's round-1 columns.  Not at
+  // L = 64: the eight words are staged in VGPRs (one SGPR operand per VALU
+  // instruction), 94 -> 106 there, which costs the fifth wave per SIMD.
+  constexpr bool UNI_PRE = !KEYED && L >= 128;
   constexpr bool SEG = MODE >= kTileSeg;              // segments of long records
   constexpr bool DO_POLY = MODE != kTileSegXor;       // Poly1305 over the ciphertext
   constexpr bool DO_XOR = MODE != kTileSegPoly;       // keystream XOR + stores
@@ -403,7 +411,15 @@ __global__ __launch_bounds__(64) void k_aead_tile(const TileArgs a) {
        super0 += (uint64_t)gridDim.x * RPS) {
   // ---- key pass: lane l -> one-time key of record super0 + l -------------
   uint32_t kr[4], kss[4];
-  F26 pw[C::LOG2G > 0 && !SEG ? C::LOG2G : 1];  // uniform / keyed: r^BPL, r^(2 BPL), ...
+  // uniform / keyed, B = BPL.  G <= 4: r^B, r^2B, r^3B, of which a lane takes
+  // the one it needs (one product per tile); wider records: r^B, r^2B, r^4B,
+  // ... for the log-tree (G - 1 distinct powers would not fit the VGPRs).
+  // Keyed G = 4 keeps the tree as well: the third power's five VGPRs take the
+  // strided sessions encrypt from 167 to 171, past the 168 of its ninth wave
+  // per CU.
+  constexpr bool ONE_PROD = !SEG && (C::G == 2 || (C::G == 4 && !KEYED));
+  constexpr int NPW = SEG || C::G == 1 ? 1 : ONE_PROD ? C::G - 1 : C::LOG2G;
+  F26 pw[NPW];
   uint32_t own_q = 0;  // kTileSeg*: the long record of segment super0 + lane
   uint32_t own_k[8], own_nlo = 0, own_nhi = 0;  // keyed modes: this lane's record
   uint32_t own_in_lo = 0, own_in_hi = 0, own_out_lo = 0, own_out_hi = 0;
@@ -440,7 +456,10 @@ __global__ __launch_bounds__(64) void k_aead_tile(const TileArgs a) {
     nxt_e = SegEntry{0u, 0u};
     if (next0 + lane < nrec) nxt_e = a.segs[dbase + next0 + lane];
   } else {
-    uint64_t n = a.nonce0 + super0 + lane;
+    // uniform: the launch's nonces share a.nonce0's high word (the host
+    // splits a batch where the low word wraps), so 32-bit arithmetic
+    uint64_t n = UNI_PRE ? join64((uint32_t)(a.nonce0 >> 32), (uint32_t)a.nonce0 + (uint32_t)super0 + lane)
+                         : a.nonce0 + super0 + lane;
     if (KEYED) {
       const uint64_t rec = super0 + lane;
       uint32_t ki = 0;
@@ -472,7 +491,12 @@ __global__ __launch_bounds__(64) void k_aead_tile(const TileArgs a) {
           own_in_lo, own_in_hi);
     }
     uint32_t otk[16];
-    chacha20_block(own_k, 0u, (uint32_t)n, (uint32_t)(n >> 32), otk);
+    if (!UNI_PRE) {
+      chacha20_block(own_k, 0u, (uint32_t)n, (uint32_t)(n >> 32), otk);
+    } else {
+      const ChaPre kpre = chacha_pre_uniform(own_k, (uint32_t)n, a.uni);
+      chacha20_block_pre(own_k, 0u, kpre, (uint32_t)n, (uint32_t)(n >> 32), otk);
+    }
     kr[0] = otk[0] & 0x0fffffffu;
     kr[1] = otk[1] & 0x0ffffffcu;
     kr[2] = otk[2] & 0x0ffffffcu;
@@ -483,8 +507,15 @@ __global__ __launch_bounds__(64) void k_aead_tile(const TileArgs a) {
 #pragma unroll
       for (int b = 0; b < C::LOG2BPL; ++b) x = mul26(x, x);
       pw[0] = x;
+      if constexpr (ONE_PROD) {
+        if constexpr (C::G == 4) {
+          pw[1] = mul26(pw[0], pw[0]);
+          pw[2] = mul26(pw[1], pw[0]);
+        }
+      } else {
 #pragma unroll
-      for (int b = 1; b < C::LOG2G; ++b) pw[b] = mul26(pw[b - 1], pw[b - 1]);
+        for (int b = 1; b < C::LOG2G; ++b) pw[b] = mul26(pw[b - 1], pw[b - 1]);
+      }
     }
   }
   (void)own_cb;
@@ -555,8 +586,8 @@ __global__ __launch_bounds__(64) void k_aead_tile(const TileArgs a) {
       bad_key = __shfl((int)own_bad, src) != 0;
     } else if (!KEYED) {
       const uint64_t n = a.nonce0 + rec0 + rho;
-      n_lo = (uint32_t)n;
-      n_hi = (uint32_t)(n >> 32);
+      n_lo = UNI_PRE ? (uint32_t)a.nonce0 + (uint32_t)rec0 + rho : (uint32_t)n;
+      n_hi = UNI_PRE ? (uint32_t)(a.nonce0 >> 32) : (uint32_t)(n >> 32);
     } else {  // kTileSegPoly: no keystream
       n_lo = n_hi = 0u;
     }
@@ -568,7 +599,7 @@ __global__ __launch_bounds__(64) void k_aead_tile(const TileArgs a) {
     ChaPre pre{};
     uint32_t ks[16];
     if (DO_XOR) {
-      pre = chacha_pre(kt, n_lo, n_hi);
+      pre = UNI_PRE ? chacha_pre_uniform(kt, n_lo, a.uni) : chacha_pre(kt, n_lo, n_hi);
       chacha20_block_pre(kt, cb, pre, n_lo, n_hi, ks);
     }
 #pragma unroll
@@ -603,6 +634,21 @@ __global__ __launch_bounds__(64) void k_aead_tile(const TileArgs a) {
       F26 h = to26(p.h0, p.h1, p.h2, p.h3, p.h4);
       if (SEG) {
         h = mul26(h, own_pw);
+      } else if constexpr (ONE_PROD) {
+        // lane j's power r^(BPL m), m = G - 1 - j, from its record's key lane
+        // (m = 0: 1): the broadcasts are LDS instructions, the choice selects
+        const uint32_t m = C::G - 1 - j;
+        F26 f;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+          uint32_t w = __shfl(pw[0].a[i], src);
+          if constexpr (C::G == 4) {
+            const uint32_t w2 = __shfl(pw[1].a[i], src), w3 = __shfl(pw[2].a[i], src);
+            w = m == 3u ? w3 : m == 2u ? w2 : w;
+          }
+          f.a[i] = m ? w : (i == 0 ? 1u : 0u);
+        }
+        h = mul26(h, f);
       } else {
         const uint32_t m = C::G - 1 - j;
 #pragma unroll
@@ -625,8 +671,22 @@ __global__ __launch_bounds__(64) void k_aead_tile(const TileArgs a) {
 #pragma unroll
         for (int i = 0; i < 5; ++i) h.a[i] += __shfl_xor(h.a[i], 1 << b);
       }
-      carry26(h);
-      carry26(h);
+      // No carry before from26, which takes any limbs < 2^31: the sum of up to
+      // 16 lanes' limbs (< 2^26 + 2^9 each) is < 2^30 + 2^13, and wider records
+      // carried at b == 4 (then at most 4 more terms of < 2^26 + 2^9 + 1).  So
+      // h4 <= 64 here instead of <= 4, and the length block's s4 <= 66:
+      //   * poly_block's column sums: four s_i r terms < 2^32 * 1.25 * 2^28
+      //     each plus s4 rr < 2^36, < 2^62.4 in all (poly_block asks for < 2^63);
+      //   * __umul24(s4, r0lo) <= 66 * 3 is exact, u5 = x4 + (x3 >> 32) < 2^31
+      //     and its fold q + (q << 2) < 2^32;
+      //   * the block leaves h4 <= 4 as after any block, which is all that
+      //     poly_final's single conditional subtraction needs.
+      // Every G therefore goes without.  The segment partial sums keep the
+      // carries: the finalize kernel reads them as P_s with a small h4.
+      if (SEG) {
+        carry26(h);
+        carry26(h);
+      }
       from26(h, p.h0, p.h1, p.h2, p.h3, p.h4);
     }
     uint32_t tag[4] = {0u, 0u, 0u, 0u};
@@ -738,6 +798,21 @@ __global__ __launch_bounds__(64) void k_aead_tile(const TileArgs a) {
       else slot = pc < (uint32_t)C::SPR ? swz<SPAN>(r * C::SPR + pc) : C::REC_SLOTS + r;
       ok = OUT_SLOTS % 64 == 0 || g < (uint32_t)OUT_SLOTS;
     };
+    // Records that must not be output as computed are rare (failed tag
+    // (decrypt): keep an in-place record, zero a copy; invalid key index:
+    // write nothing): their pieces' flags and data change behind a
+    // wave-uniform branch.  Merged back into one store sequence, the flags
+    // become a VGPR each (a v_cndmask before the branch, a v_and and a v_cmp
+    // after it, per piece and tile: 48 VALU per 1 KiB tile).  From 1 KiB on a
+    // tile with such a record takes its own copy of the whole gather-and-store
+    // sequence instead, and the common copy's guards stay scalar compares.
+    // Shorter records keep the merge: L = 512 runs at 243..256 VGPRs and the
+    // second copy pushes it into AGPRs, i.e. to one wave per SIMD.
+    constexpr bool SPLIT_FAILED = (DECRYPT || KEYED) && L >= 1024;
+    const bool any_failed = (DECRYPT || KEYED) && fail_mask != 0;
+#pragma unroll
+    for (int copy = 0; copy < (SPLIT_FAILED ? 2 : 1); ++copy) {  // 0: common (or merged), 1: failed
+    if (SPLIT_FAILED && any_failed != (copy == 1)) continue;
 #pragma unroll
     for (int part = 0; part < NPART; ++part) {
       const int q0 = part * NQ;
@@ -753,11 +828,7 @@ __global__ __launch_bounds__(64) void k_aead_tile(const TileArgs a) {
         st[qq] = ok && (full || r < nv);
         ov[qq] = lb[slot < (uint32_t)C::NSLOT ? slot : 0u];
       }
-      // Records that must not be output as computed (rare; a separate,
-      // wave-uniform branch so the common path carries none of this):
-      // failed tag (decrypt): keep an in-place record, zero a copy; invalid
-      // key index: write nothing.
-      if ((DECRYPT || KEYED) && fail_mask != 0) {
+      if (SPLIT_FAILED ? copy == 1 : any_failed) {
 #pragma unroll
         for (int qq = 0; qq < NQ; ++qq) {
           const int q = q0 + qq;
@@ -812,6 +883,7 @@ __global__ __launch_bounds__(64) void k_aead_tile(const TileArgs a) {
         if (store) store16<true>(dst, ov[qq], 16);
       }
     }
+    }  // copies
     prev_all = ABL == 0 && full && fail_mask == 0;
   }
   }  // super-tiles

@@ -10,6 +10,10 @@
 //     record gets no store at all in place, zeros as a copy; no store past
 //     [out + i*stride, + len) -- no byte of unverified plaintext is stored.
 //   emu_uniform <seed> <len>...      (default: the length list below)
+//   emu_uniform tile                 the exact tile kernel (tile_kernel.hpp):
+//     G = 2, 4 (one recombination product per lane), 8 and 64 (the log-tree),
+//     partial tiles and super-tiles, nonce ranges that cross 2^32 (the host's
+//     split into two launches) or end at 2^64 - 1, all-0xFF / all-0x00 records
 // Test infrastructure only (links oracle/chachapoly_oracle.c).
 #include <algorithm>
 #include <atomic>
@@ -51,6 +55,7 @@ struct Ext {
 };
 static std::vector<Ext> g_ext;
 static bool g_inplace = false;
+static bool g_packed = false;
 static std::atomic<long> g_outside{0}, g_unverified{0};
 static void watch(const void *dst, const void *data, int n) {
   const uintptr_t a = reinterpret_cast<uintptr_t>(dst), b = a + (uintptr_t)n;
@@ -66,19 +71,25 @@ static void watch(const void *dst, const void *data, int n) {
   if (nz) g_unverified.fetch_add(1);
 }
 
-static void run(uint32_t L, uint64_t seed, bool inplace, uint64_t R) {
+// fill: 0 = pseudo-random records, 1 = all 0xFF, 2 = all 0x00
+static void run(uint32_t L, uint64_t seed, bool inplace, uint64_t R, const uint64_t *nonce = nullptr,
+                int fill = 0) {
   const uint64_t c16 = (L + 15) / 16 * 16, ct16 = (L + 31) / 16 * 16;
   // padded strides: records start 16-byte aligned, with gaps after them
-  const uint64_t sin = inplace ? ct16 + 32 : c16 + 16 * (seed % 3), sct = inplace ? sin : ct16 + 32;
+  // g_packed (copies of 16-byte multiples): back to back, the tile kernel's contiguous variant
+  const bool packed = g_packed && !inplace && L % 16 == 0;
+  const uint64_t sin = packed ? L : inplace ? ct16 + 32 : c16 + 16 * (seed % 3);
+  const uint64_t sct = packed ? L + 16 : inplace ? sin : ct16 + 32;
   uint8_t key[32];
   for (int i = 0; i < 32; ++i) key[i] = (uint8_t)(mix64(seed + i) | 1);
   uint32_t k[8];
   std::memcpy(k, key, 32);
-  const uint64_t nonce0 = mix64(seed * 5 + L) & 0xffffffffull;
+  const uint64_t nonce0 = nonce ? *nonce : mix64(seed * 5 + L) & 0xffffffffull;
   // exact-size buffers (ASan): the masked kernel reads whole 16-byte pieces,
   // so the buffers end on a 16-byte boundary, as any allocation does on the GPU
   std::vector<uint8_t> pt_ref(R * L);
-  for (uint64_t j = 0; j < R * L; ++j) pt_ref[j] = (uint8_t)mix64(seed * 131 + j);
+  for (uint64_t j = 0; j < R * L; ++j)
+    pt_ref[j] = fill == 1 ? 0xFF : fill == 2 ? 0x00 : (uint8_t)mix64(seed * 131 + j);
   uint8_t *pt = (uint8_t *)std::aligned_alloc(16, R * sin);
   uint8_t *ct = inplace ? pt : (uint8_t *)std::aligned_alloc(16, R * sct);
   std::memset(pt, 0xA5, R * sin);
@@ -262,6 +273,32 @@ int main(int argc, char **argv) {
       std::fflush(stdout);
     }
     noise_amd::records_scratch_release(nullptr);  // the staging scratch
+    std::printf("%s (%d failures)\n", fails ? "FAIL" : "ok", fails);
+    return fails ? 1 : 0;
+  }
+  if (argc > 1 && std::strcmp(argv[1], "tile") == 0) {
+    const uint64_t edges[] = {(1ull << 32) - 70, (1ull << 32) - 64, ~0ull - 129, 0};
+    auto both = [](uint32_t L, uint64_t R, const uint64_t *nonce, int fill) {
+      g_packed = true;
+      run(L, 15 + L + R, false, R, nonce, fill);
+      g_packed = false;
+      run(L, 17 + L + R, false, R, nonce, fill);
+      run(L, 19 + L + 3 * R, true, R, nonce, fill);
+    };
+    for (uint32_t L : {512u, 1024u, 2048u, 16384u}) {
+      for (uint64_t R : {1, 15, 17, 65, 130}) {
+        if (L == 16384 && R > 17) continue;  // one record per tile: 17 are two super-tile rounds here
+        const uint64_t n0 = (1ull << 32) - R / 2;  // crosses 2^32 inside the batch (R > 1)
+        both(L, R, &n0, 0);
+      }
+      std::printf("tile L=%u ok so far (%d failures)\n", L, fails);
+      std::fflush(stdout);
+    }
+    for (uint64_t n0 : edges) both(1024, 130, &n0, 0);
+    for (uint32_t L : {1024u, 16384u})
+      for (int fill : {1, 2}) both(L, L == 1024 ? 65 : 3, nullptr, fill);
+    std::printf("uniform tile: %ld stores outside, %ld stores of unverified plaintext\n", g_outside.load(),
+                g_unverified.load());
     std::printf("%s (%d failures)\n", fails ? "FAIL" : "ok", fails);
     return fails ? 1 : 0;
   }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include "tile_kernel.hpp"
+#include "tile_launch.hpp"
 using namespace noise_amd;
 int main() {
   const uint64_t R = 1 << 20;
@@ -30,7 +31,8 @@ int main() {
   };
   const dim3 g(R / 64), b(64);
   TileArgs ea{}, da{};
-  ea.key = key; ea.in = in; ea.in_stride = L; ea.out = out; ea.out_stride = L + 16; ea.nrec = R;
+  tile_set_uniform(ea, key, 0);
+  ea.in = in; ea.in_stride = L; ea.out = out; ea.out_stride = L + 16; ea.nrec = R;
   da = ea; da.in = out; da.in_stride = L + 16; da.out = in; da.out_stride = L; da.status = out;
   for (int rep = 0; rep < 2; ++rep) {
     timeit("full", [&] { hipLaunchKernelGGL((k_aead_tile<false, 1024, true, kTileUniform, 0>), g, b, 0, 0, ea); });
