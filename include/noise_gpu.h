@@ -419,6 +419,99 @@ int noise_gpu_cs_decrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess, cons
                                   uint64_t in_stride, uint8_t *d_out, uint64_t out_stride,
                                   uint32_t len, uint8_t *d_status, uint64_t nrec, void *stream);
 
+/* ---- out-of-order receive on a table: replay windows ---------------------
+ * For datagram transports (Noise spec 11.4): the sender puts n on the wire
+ * (noise_gpu_cs_encrypt_records writes the assigned nonces into the
+ * descriptors, noise_gpu_cs_assign into an array), the receiver decrypts with
+ * that explicit nonce -- the reference's hook is CipherState::set_nonce,
+ * noise.h:109 -- and rejects replays itself.  Each session of a table gets a
+ * sliding window in HBM, allocated and zeroed on the first call below:
+ *   next  one past the highest accepted nonce; 0 = nothing accepted yet
+ *   bits  NOISE_GPU_CS_WINDOW of them: bit n mod 1024 says nonce n of
+ *         [next - 1024, next) was accepted.  All-zero is the fresh state.
+ *   check(n):  n >= next: fresh.  next - n > 1024: too old.  Otherwise fresh
+ *              iff the bit is clear.
+ *   update(n), only after check(n) passed: if n >= next, clear the bits of
+ *              the nonces next .. n (all 1024 if n - next + 1 >= 1024) and set
+ *              next = n + 1; then set bit n.
+ * The table's in-order counter n is neither read nor moved by these calls,
+ * and a table that never uses them behaves as before.
+ *
+ * A windowed decrypt does, per session, exactly what this loop over the
+ * batch in record order does:
+ *   s >= nsess or keyless row -> REC_BAD_KEY (not processed, nothing written,
+ *                                no table memory touched for s >= nsess)
+ *   nonce >= 2^64-2           -> REC_NONCE   (not processed, nothing written;
+ *                                the reference's limit, noise.cpp:416-418)
+ *   !check(nonce)             -> REC_REPLAY
+ *   tag does not verify       -> REC_BAD_MAC (window untouched; output as the
+ *                                other decrypts: in place untouched, copy zeroed)
+ *   else update(nonce)        -> REC_OK
+ * Only the OUTPUT BYTES of a REC_REPLAY record can differ from the loop's: a
+ * record that the window state AT ENTRY already rejects is not decrypted and
+ * nothing is written to its output; a record that passes that test and
+ * verifies, but whose nonce an earlier record of the same batch took or slid
+ * past, has its len output bytes zeroed, in place or not (its plaintext was
+ * computed before the verdict).
+ *
+ * Why the batch may run in parallel: next never decreases, and a set bit stays
+ * set until it slides out, after which its nonce is too old -- so a nonce
+ * rejected against the entry state is rejected against every later state; a
+ * record is a replay of an earlier record of the batch iff an earlier VERIFIED
+ * record of its session carries the same nonce; and the running next before a
+ * verified record is max(next at entry, 1 + max nonce of the verified records
+ * before it in its session): rejected records never raise it.  A record whose
+ * tag fails takes its turn in the same order and only looks.  The result is
+ * deterministic (the same stable sort as assignment, no atomics on global
+ * memory).
+ *
+ * Argument rules as for the calls above: strided arrays aligned to 4 / 8 with
+ * strides that are multiples of 4 / 8, nrec <= 2^31, d_status required, one
+ * stream at a time, everything stream-ordered without host synchronisation;
+ * back-to-back batches on one stream see each other's windows.  Scratch is the
+ * table's.  noise_gpu_cs_set WITH keys also resets those sessions' windows once
+ * the rows exist (a new key starts a new nonce space); rekey leaves them;
+ * noise_gpu_cs_destroy wipes them.
+ *
+ * The names are noise_gpu_cswin_*, not noise_gpu_cs_window_*: the
+ * noise_gpu_cs_* prefix names the closed set of in-order table calls. */
+#define NOISE_GPU_REC_REPLAY 4u /* nonce too old or already accepted */
+#define NOISE_GPU_CS_WINDOW 1024u
+/* fresh windows for sessions [first, first + count) */
+int noise_gpu_cswin_reset(noise_gpu_cs *cs, uint64_t first, uint64_t count, void *stream);
+/* copy out next (8 bytes each) and / or the bitmaps (128-byte rows: bit n mod
+ * 1024 is bit (n & 7) of byte (n mod 1024) / 8) of [first, first + count);
+ * either pointer may be NULL.  Fresh state if the table never used a window. */
+int noise_gpu_cswin_get(const noise_gpu_cs *cs, uint64_t first, uint64_t count,
+                        uint64_t *d_next, uint8_t *d_bits, void *stream);
+/* The primitives, strided like noise_gpu_cs_assign (here d_nonce is read).
+ * filter: d_status[i] = REC_BAD_KEY / REC_NONCE / REC_REPLAY against the
+ * windows as they are, else REC_OK; read-only on the table. */
+int noise_gpu_cswin_filter(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t sess_stride,
+                           const uint8_t *d_nonce, uint64_t nonce_stride,
+                           uint8_t *d_status, uint64_t nrec, void *stream);
+/* commit: d_status[i] == REC_OK on entry marks a verified record; those are
+ * taken per session in record order through check / update, and the losers
+ * become REC_REPLAY (REC_BAD_KEY / REC_NONCE for an index >= nsess / a nonce
+ * >= 2^64-2).  REC_BAD_MAC marks a record whose tag failed: it moves nothing,
+ * and becomes REC_REPLAY where check fails when its turn comes (the loop looks
+ * at the window before the tag).  Other entries are left as they are. */
+int noise_gpu_cswin_commit(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t sess_stride,
+                           const uint8_t *d_nonce, uint64_t nonce_stride,
+                           uint8_t *d_status, uint64_t nrec, void *stream);
+/* filter + noise_gpu_decrypt_records_sized over the table's key rows + commit;
+ * key_idx is the session, nonce the wire's (d_recs is not written). */
+int noise_gpu_cswin_decrypt_records(noise_gpu_cs *cs, const noise_gpu_record *d_recs,
+                                    uint64_t nrec, const uint8_t *d_in, uint8_t *d_out,
+                                    const uint8_t *d_ad, uint8_t *d_status, uint64_t len_sum,
+                                    void *stream);
+/* the same over noise_gpu_decrypt_sessions (its shapes; NOISE_GPU_E_ARG
+ * otherwise): record i belongs to session d_sess[i] with nonce d_nonces[i]. */
+int noise_gpu_cswin_decrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess,
+                                     const uint64_t *d_nonces, const uint8_t *d_in,
+                                     uint64_t in_stride, uint8_t *d_out, uint64_t out_stride,
+                                     uint32_t len, uint8_t *d_status, uint64_t nrec, void *stream);
+
 /* ---- host-buffer entry points (synchronous) ----------------------------
  * Used by the CipherState shim for single records (encrypt_with_ad /
  * decrypt_with_ad / rekey).  A record of <= 65535 bytes with <= 8192 bytes of

@@ -32,13 +32,11 @@
 // One-wave workgroups throughout; grids are capped (NOISE_GRID_CAP) and
 // stride over their work.
 #include "chachapoly_device.hpp"
+#include "cstate_device.hpp"
 #include "launchers.hpp"
 
 namespace noise_amd {
 
-#ifndef NOISE_GRID_CAP  // as records_kernels.hip; overridable for the CPU emulation build
-#define NOISE_GRID_CAP 8192u
-#endif
 // Sort geometry: wave w owns records [w*chunk, (w+1)*chunk); at most
 // kCsWaves waves (the scan's lane-owns-a-run layout: kCsWaves / 64 per lane).
 #ifndef NOISE_CS_WAVES
@@ -53,14 +51,8 @@ static_assert(kCsWaves % 64 == 0 && kCsMinChunk % 64 == 0, "sort geometry");
 constexpr uint32_t kCsBins = 256;
 // steps (64 records each) whose loads a wave issues before it ranks them
 constexpr int kCsBatch = 8;
-constexpr uint32_t kCsRefused = 0xffffffffu;  // the mark: never a session (nsess <= 2^32-2)
 
 namespace {
-
-inline unsigned cs_capped(uint64_t want) {
-  if (want == 0) want = 1;
-  return (unsigned)(want < NOISE_GRID_CAP ? want : NOISE_GRID_CAP);
-}
 
 struct CsGeom {
   uint32_t nw, chunk;
@@ -120,16 +112,6 @@ __device__ __forceinline__ uint64_t cs_match(uint32_t v, int bits, bool live) {
     m &= bit ? bm : ~bm;
   }
   return m;
-}
-
-__device__ __forceinline__ bool cs_key_zero(const uint8_t *keys, uint32_t s) {
-  const uint4 *kp = reinterpret_cast<const uint4 *>(keys + 32ull * s);
-  const uint4 a = kp[0], b = kp[1];
-  return (a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w) == 0u;
-}
-
-__device__ __forceinline__ uint32_t cs_sess_at(const uint8_t *sess, uint64_t stride, uint64_t i) {
-  return *reinterpret_cast<const uint32_t *>(sess + i * stride);
 }
 
 // where a record's results go (CsAssign, launchers.hpp)
@@ -427,12 +409,52 @@ __global__ __launch_bounds__(64) void k_cs_rekey(uint8_t *keys, uint32_t nsess, 
 size_t cs_assign_scratch_bytes(uint64_t nrec) {
   return nrec <= 64 ? 0 : cs_carve(nullptr, nullptr, nrec);
 }
+size_t cs_sort_scratch_bytes(uint64_t nrec) { return cs_carve(nullptr, nullptr, nrec); }
 
 // bytes of nsess - 1 (at least one): the radix passes
 static int cs_passes(uint32_t nsess) {
   int p = 1;
   for (uint32_t v = (nsess - 1u) >> 8; v; v >>= 8) ++p;
   return p;
+}
+
+// the stable sort of (session, record index) pairs by session: *out names the
+// sorted pairs [0, hdr[0]) inside `scratch` (cs_sort_scratch_bytes(nrec));
+// indices >= nsess are dropped (and reported BAD_KEY in status, if given)
+hipError_t launch_cs_sort(const uint8_t *sess, uint64_t sess_stride, uint32_t nsess, uint64_t nrec64,
+                          void *scratch, uint8_t *status, hipStream_t stream, CsSorted *out) {
+  CsScratch s;
+  cs_carve(&s, static_cast<uint8_t *>(scratch), nrec64);
+  const CsGeom g = cs_geom(nrec64);
+  const uint32_t nrec = (uint32_t)nrec64;
+  const dim3 b64(64);
+  const dim3 gw(cs_capped(g.nw)), gd(cs_capped(kCsBins));
+  const int passes = cs_passes(nsess);
+  int cur = 0;  // (key, val)[cur] holds the last pass's output
+  for (int p = 0; p < passes; ++p) {
+    const int shift = 8 * p;
+    if (p == 0) {
+      hipLaunchKernelGGL(k_cs_count<true>, gw, b64, 0, stream, sess, sess_stride, nsess,
+                         (const unsigned long long *)nullptr, (const uint32_t *)s.hdr, nrec, g.chunk,
+                         g.nw, shift, s.part);
+      hipLaunchKernelGGL(k_cs_scan, gd, b64, 0, stream, s.part, g.nw, s.tot);
+      hipLaunchKernelGGL(k_cs_scatter<true>, gw, b64, 0, stream, sess, sess_stride, nsess,
+                         (const unsigned long long *)nullptr, s.hdr, nrec, g.chunk, g.nw, shift,
+                         (const uint32_t *)s.part, (const uint32_t *)s.tot, s.pair[0], status);
+      cur = 0;
+    } else {
+      const unsigned long long *pin = s.pair[cur];
+      hipLaunchKernelGGL(k_cs_count<false>, gw, b64, 0, stream, sess, sess_stride, nsess, pin,
+                         (const uint32_t *)s.hdr, nrec, g.chunk, g.nw, shift, s.part);
+      hipLaunchKernelGGL(k_cs_scan, gd, b64, 0, stream, s.part, g.nw, s.tot);
+      hipLaunchKernelGGL(k_cs_scatter<false>, gw, b64, 0, stream, sess, sess_stride, nsess, pin,
+                         s.hdr, nrec, g.chunk, g.nw, shift, (const uint32_t *)s.part,
+                         (const uint32_t *)s.tot, s.pair[cur ^ 1], (uint8_t *)nullptr);
+      cur ^= 1;
+    }
+  }
+  *out = CsSorted{s.pair[cur], s.hdr};
+  return hipGetLastError();
 }
 
 hipError_t launch_cs_assign(const CsTableView &t, const CsAssign &a, void *scratch,
@@ -447,37 +469,13 @@ hipError_t launch_cs_assign(const CsTableView &t, const CsAssign &a, void *scrat
                        t.nsess, bits, (uint32_t)a.nrec, o);
     return hipGetLastError();
   }
-  CsScratch s;
-  cs_carve(&s, static_cast<uint8_t *>(scratch), a.nrec);
-  const CsGeom g = cs_geom(a.nrec);
-  const uint32_t nrec = (uint32_t)a.nrec;
-  const dim3 gw(cs_capped(g.nw)), gd(cs_capped(kCsBins)), gr(cs_capped((a.nrec + 63) / 64));
-  const int passes = cs_passes(t.nsess);
-  int cur = 0;  // (key, val)[cur] holds the last pass's output
-  for (int p = 0; p < passes; ++p) {
-    const int shift = 8 * p;
-    if (p == 0) {
-      hipLaunchKernelGGL(k_cs_count<true>, gw, b64, 0, stream, a.sess, a.sess_stride, t.nsess,
-                         (const unsigned long long *)nullptr, (const uint32_t *)s.hdr, nrec, g.chunk,
-                         g.nw, shift, s.part);
-      hipLaunchKernelGGL(k_cs_scan, gd, b64, 0, stream, s.part, g.nw, s.tot);
-      hipLaunchKernelGGL(k_cs_scatter<true>, gw, b64, 0, stream, a.sess, a.sess_stride, t.nsess,
-                         (const unsigned long long *)nullptr, s.hdr, nrec, g.chunk, g.nw, shift,
-                         (const uint32_t *)s.part, (const uint32_t *)s.tot, s.pair[0], a.status);
-      cur = 0;
-    } else {
-      const unsigned long long *pin = s.pair[cur];
-      hipLaunchKernelGGL(k_cs_count<false>, gw, b64, 0, stream, a.sess, a.sess_stride, t.nsess, pin,
-                         (const uint32_t *)s.hdr, nrec, g.chunk, g.nw, shift, s.part);
-      hipLaunchKernelGGL(k_cs_scan, gd, b64, 0, stream, s.part, g.nw, s.tot);
-      hipLaunchKernelGGL(k_cs_scatter<false>, gw, b64, 0, stream, a.sess, a.sess_stride, t.nsess, pin,
-                         s.hdr, nrec, g.chunk, g.nw, shift, (const uint32_t *)s.part,
-                         (const uint32_t *)s.tot, s.pair[cur ^ 1], (uint8_t *)nullptr);
-      cur ^= 1;
-    }
-  }
-  const unsigned long long *pair = s.pair[cur];
-  const uint32_t *hdr = s.hdr;
+  CsSorted sorted;
+  const hipError_t e =
+      launch_cs_sort(a.sess, a.sess_stride, t.nsess, a.nrec, scratch, a.status, stream, &sorted);
+  if (e != hipSuccess) return e;
+  const dim3 gr(cs_capped((a.nrec + 63) / 64));
+  const unsigned long long *pair = sorted.pair;
+  const uint32_t *hdr = sorted.hdr;
   hipLaunchKernelGGL(k_cs_heads, gr, b64, 0, stream, pair, hdr, t.start);
   hipLaunchKernelGGL(k_cs_apply, gr, b64, 0, stream, pair, hdr, (const uint32_t *)t.start,
                      (const uint8_t *)t.keys, (const uint64_t *)t.ctr, o);

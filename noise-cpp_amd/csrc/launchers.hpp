@@ -216,6 +216,18 @@ struct CsAssign {
 size_t cs_assign_scratch_bytes(uint64_t nrec);
 hipError_t launch_cs_assign(const CsTableView &t, const CsAssign &a, void *scratch,
                             hipStream_t stream);
+// The sort launch_cs_assign ranks with, for other callers (cswin_kernels.hip):
+// a stable sort of (session, record index) pairs by session.  *out names the
+// sorted pairs [0, hdr[0]) -- record index << 32 | session -- inside `scratch`
+// (cs_sort_scratch_bytes(nrec) bytes, nrec > 0); records whose index is
+// >= nsess are dropped, and get BAD_KEY in `status` if that is given.
+struct CsSorted {
+  const unsigned long long *pair;
+  const uint32_t *hdr;  // [0] = the records kept
+};
+size_t cs_sort_scratch_bytes(uint64_t nrec);
+hipError_t launch_cs_sort(const uint8_t *sess, uint64_t sess_stride, uint32_t nsess, uint64_t nrec,
+                          void *scratch, uint8_t *status, hipStream_t stream, CsSorted *out);
 // status[i] = NOISE_GPU_REC_NONCE where the private index differs from the caller's
 hipError_t launch_cs_fix(const uint8_t *sess, uint64_t sess_stride, const uint8_t *kill,
                          uint64_t kill_stride, uint8_t *status, uint64_t nrec, hipStream_t stream);
@@ -225,6 +237,38 @@ hipError_t launch_cs_set(const CsTableView &t, uint64_t first, uint64_t count, c
 // REKEY of sess[0..count), or of sessions [0, count) when sess is null
 hipError_t launch_cs_rekey(const CsTableView &t, const uint32_t *sess, uint64_t count,
                            hipStream_t stream);
+
+// ---- replay windows of a CipherState table (cswin_kernels.hip) -----------
+struct CsWindowView {
+  uint64_t *next;  // [nsess] one past the highest accepted nonce
+  uint32_t *bits;  // [nsess][32] bit n mod 1024 of nonce n in [next - 1024, next)
+};
+// One batch: record i belongs to session *(uint32_t *)(sess + i * sess_stride)
+// and carries the nonce *(uint64_t *)(nonce + i * nonce_stride).
+struct CwBatch {
+  const uint8_t *sess;
+  uint64_t sess_stride;
+  const uint8_t *nonce;
+  uint64_t nonce_stride;
+  uint64_t nrec;  // <= 2^31
+};
+// pre[i] = BAD_KEY / NONCE / REPLAY against the windows as they are, else OK;
+// a refused record sets the uint32 at kill + i * kill_stride (if given) to
+// 0xffffffff.  Read-only on the table.
+hipError_t launch_cw_filter(const CsTableView &t, const CsWindowView &w, const CwBatch &b,
+                            uint8_t *pre, uint8_t *kill, uint64_t kill_stride, hipStream_t stream);
+// the records with status OK, per session in record order: check / update;
+// the losers' status becomes REPLAY (BAD_KEY / NONCE for an index or a nonce
+// out of range)
+size_t cw_commit_scratch_bytes(uint64_t nrec);
+hipError_t launch_cw_commit(const CsTableView &t, const CsWindowView &w, const CwBatch &b,
+                            uint8_t *status, void *scratch, hipStream_t stream);
+// status[i] = pre[i] where that is not OK; the output of a record that is OK
+// in pre and REPLAY in status is zeroed: (recs[i].out_off, recs[i].len), or
+// (i * out_stride, len) when recs is null
+hipError_t launch_cw_finish(const uint8_t *pre, uint8_t *status, const noise_gpu_record *recs,
+                            uint8_t *out, uint64_t out_stride, uint32_t len, uint64_t nrec,
+                            hipStream_t stream);
 
 // C-ABI helpers shared by the API translation units (noise_gpu_api.hip)
 int api_hip_fail(hipError_t e, const char *what);

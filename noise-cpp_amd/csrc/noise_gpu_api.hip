@@ -796,6 +796,7 @@ int noise_gpu_rekey_keys(uint8_t *d_keys, uint64_t nkeys, void *stream) {
 // the device current at create
 struct noise_gpu_cs {
   noise_amd::CsTableView t{};
+  noise_amd::CsWindowView w{};  // replay windows: allocated by the first windowed call
   void *scratch = nullptr;  // grow-only; the sort's tables and the private index / nonce copies
   size_t scratch_size = 0;
 };
@@ -804,6 +805,7 @@ namespace {
 
 constexpr uint64_t kCsMaxSess = 0xfffffffeull;  // 2^32-2: 0xffffffff marks a refused record
 constexpr uint64_t kCsMaxRec = 1ull << 31;
+constexpr uint64_t kCsWinRow = NOISE_GPU_CS_WINDOW / 8;  // bytes of a session's bitmap
 
 // the table's scratch, >= bytes; the smaller one is wiped and freed
 // stream-ordered after the launches that still use it
@@ -905,6 +907,47 @@ int cs_sessions(bool decrypt, noise_gpu_cs *cs, const uint32_t *d_sess, const ui
   return NOISE_GPU_OK;
 }
 
+// ---- replay windows ----
+hipError_t cs_window_clear(noise_gpu_cs *cs, uint64_t first, uint64_t count, hipStream_t st) {
+  if (count == 0) return hipSuccess;
+  hipError_t e = hipMemsetAsync(cs->w.next + first, 0, 8 * count, st);
+  if (e != hipSuccess) return e;
+  return hipMemsetAsync(reinterpret_cast<uint8_t *>(cs->w.bits) + kCsWinRow * first, 0,
+                        kCsWinRow * count, st);
+}
+
+// the window rows, fresh on the first call
+hipError_t cs_window_rows(noise_gpu_cs *cs, hipStream_t st) {
+  if (cs->w.next) return hipSuccess;
+  const uint64_t n = cs->t.nsess;
+  void *next = nullptr, *bits = nullptr;
+  hipError_t e = noise_amd::dev_alloc(&next, 8 * n, st);
+  if (e != hipSuccess) return e;
+  if ((e = noise_amd::dev_alloc(&bits, kCsWinRow * n, st)) != hipSuccess) {
+    (void)noise_amd::dev_wipe_free(next, 0, st);
+    return e;
+  }
+  cs->w.next = static_cast<uint64_t *>(next);
+  cs->w.bits = static_cast<uint32_t *>(bits);
+  return cs_window_clear(cs, 0, n, st);
+}
+
+// the three phases of a windowed decrypt around the AEAD launch `aead`, which
+// works on the private index at `kill`; scratch: commit | pre-status | priv
+template <class Aead>
+int cs_window_decrypt(noise_gpu_cs *cs, const noise_amd::CwBatch &b, size_t commit_bytes,
+                      uint8_t *kill, uint64_t kill_stride, const noise_gpu_record *recs,
+                      uint8_t *d_out, uint64_t out_stride, uint32_t len, uint8_t *d_status,
+                      hipStream_t st, Aead aead) {
+  uint8_t *base = static_cast<uint8_t *>(cs->scratch);
+  uint8_t *pre = base + commit_bytes;
+  HIP_TRY(noise_amd::launch_cw_filter(cs->t, cs->w, b, pre, kill, kill_stride, st));
+  HIP_TRY(aead());
+  HIP_TRY(noise_amd::launch_cw_commit(cs->t, cs->w, b, d_status, base, st));
+  HIP_TRY(noise_amd::launch_cw_finish(pre, d_status, recs, d_out, out_stride, len, b.nrec, st));
+  return NOISE_GPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -947,6 +990,8 @@ int noise_gpu_cs_destroy(noise_gpu_cs *cs) {
   keep(hipMemset(cs->t.keys, 0, n * 32));
   keep(hipMemset(cs->t.ctr, 0, n * 8));
   keep(hipMemset(cs->t.start, 0, n * 4));
+  keep(noise_amd::dev_wipe_free(cs->w.next, n * 8, nullptr));
+  keep(noise_amd::dev_wipe_free(cs->w.bits, n * kCsWinRow, nullptr));
   keep(noise_amd::dev_wipe_free(cs->scratch, cs->scratch_size, nullptr));
   keep(hipDeviceSynchronize());
   (void)hipFree(cs->t.keys);
@@ -965,6 +1010,8 @@ int noise_gpu_cs_set(noise_gpu_cs *cs, uint64_t first, uint64_t count, const uin
   if (!d_keys && !d_n) return arg_fail("neither key rows nor counters given");
   if ((rc = check_device())) return rc;
   HIP_TRY(noise_amd::launch_cs_set(cs->t, first, count, d_keys, key_stride, d_n, (hipStream_t)stream));
+  // a new key starts a new nonce space
+  if (d_keys && cs->w.next) HIP_TRY(cs_window_clear(cs, first, count, (hipStream_t)stream));
   return NOISE_GPU_OK;
 }
 
@@ -1027,6 +1074,133 @@ int noise_gpu_cs_decrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess, cons
                                   uint64_t in_stride, uint8_t *d_out, uint64_t out_stride,
                                   uint32_t len, uint8_t *d_status, uint64_t nrec, void *stream) {
   return cs_sessions(true, cs, d_sess, d_in, in_stride, d_out, out_stride, len, d_status, nrec, stream);
+}
+
+int noise_gpu_cswin_reset(noise_gpu_cs *cs, uint64_t first, uint64_t count, void *stream) {
+  int rc = cs_check_range(cs, first, count);
+  if (rc || count == 0) return rc;
+  if ((rc = check_device())) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  const bool fresh = !cs->w.next;
+  HIP_TRY(cs_window_rows(cs, st));
+  if (!fresh) HIP_TRY(cs_window_clear(cs, first, count, st));
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cswin_get(const noise_gpu_cs *cs, uint64_t first, uint64_t count, uint64_t *d_next,
+                        uint8_t *d_bits, void *stream) {
+  if (reinterpret_cast<uintptr_t>(d_next) & 7u) return arg_fail("next array must be 8-byte aligned");
+  int rc = cs_check_range(cs, first, count);
+  if (rc || count == 0) return rc;
+  if ((rc = check_device())) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  if (!cs->w.next) {  // never used a window: the fresh state
+    if (d_next) HIP_TRY(hipMemsetAsync(d_next, 0, 8 * count, st));
+    if (d_bits) HIP_TRY(hipMemsetAsync(d_bits, 0, kCsWinRow * count, st));
+    return NOISE_GPU_OK;
+  }
+  if (d_next)
+    HIP_TRY(hipMemcpyAsync(d_next, cs->w.next + first, 8 * count, hipMemcpyDeviceToDevice, st));
+  if (d_bits)
+    HIP_TRY(hipMemcpyAsync(d_bits, reinterpret_cast<const uint8_t *>(cs->w.bits) + kCsWinRow * first,
+                           kCsWinRow * count, hipMemcpyDeviceToDevice, st));
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cswin_filter(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t sess_stride,
+                           const uint8_t *d_nonce, uint64_t nonce_stride, uint8_t *d_status,
+                           uint64_t nrec, void *stream) {
+  int rc = cs_check_assign(cs, d_sess, sess_stride, d_nonce, nonce_stride, nrec);
+  if (rc || nrec == 0) return rc;
+  if (!d_status) return arg_fail("null status buffer");
+  if ((rc = check_device())) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(cs_window_rows(cs, st));
+  const noise_amd::CwBatch b{d_sess, sess_stride, d_nonce, nonce_stride, nrec};
+  HIP_TRY(noise_amd::launch_cw_filter(cs->t, cs->w, b, d_status, nullptr, 0, st));
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cswin_commit(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t sess_stride,
+                           const uint8_t *d_nonce, uint64_t nonce_stride, uint8_t *d_status,
+                           uint64_t nrec, void *stream) {
+  int rc = cs_check_assign(cs, d_sess, sess_stride, d_nonce, nonce_stride, nrec);
+  if (rc || nrec == 0) return rc;
+  if (!d_status) return arg_fail("null status buffer");
+  if ((rc = check_device())) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(cs_window_rows(cs, st));
+  HIP_TRY(cs_scratch(cs, noise_amd::cw_commit_scratch_bytes(nrec), st));
+  const noise_amd::CwBatch b{d_sess, sess_stride, d_nonce, nonce_stride, nrec};
+  HIP_TRY(noise_amd::launch_cw_commit(cs->t, cs->w, b, d_status, cs->scratch, st));
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cswin_decrypt_records(noise_gpu_cs *cs, const noise_gpu_record *d_recs, uint64_t nrec,
+                                    const uint8_t *d_in, uint8_t *d_out, const uint8_t *d_ad,
+                                    uint8_t *d_status, uint64_t len_sum, void *stream) {
+  if (nrec > kCsMaxRec) return arg_fail("more than 2^31 records in one batch");
+  if (!cs) return arg_fail("null table");
+  if (nrec == 0) return NOISE_GPU_OK;
+  if (!d_recs || !d_in || !d_out || !d_status) return arg_fail("null descriptors / buffers / status");
+  if (reinterpret_cast<uintptr_t>(d_recs) & 7u) return arg_fail("descriptors must be 8-byte aligned");
+  int rc = check_device();
+  if (rc) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(cs_window_rows(cs, st));
+  // scratch: the commit's | the prefilter's verdicts | a private copy of the
+  // descriptors, in which a refused record's key_idx is out of range
+  const size_t commit_bytes = align16(noise_amd::cw_commit_scratch_bytes(nrec));
+  const size_t pre_bytes = align16(nrec);
+  HIP_TRY(cs_scratch(cs, commit_bytes + pre_bytes + nrec * sizeof(noise_gpu_record), st));
+  uint8_t *base = static_cast<uint8_t *>(cs->scratch);
+  noise_gpu_record *priv = reinterpret_cast<noise_gpu_record *>(base + commit_bytes + pre_bytes);
+  HIP_TRY(hipMemcpyAsync(priv, d_recs, nrec * sizeof(noise_gpu_record), hipMemcpyDeviceToDevice, st));
+  constexpr uint64_t kRec = sizeof(noise_gpu_record);
+  const uint8_t *caller = reinterpret_cast<const uint8_t *>(d_recs);
+  const noise_amd::CwBatch b{caller + offsetof(noise_gpu_record, key_idx), kRec,
+                             caller + offsetof(noise_gpu_record, nonce), kRec, nrec};
+  return cs_window_decrypt(
+      cs, b, commit_bytes, reinterpret_cast<uint8_t *>(priv) + offsetof(noise_gpu_record, key_idx), kRec,
+      d_recs, d_out, 0, 0, d_status, st, [&] {
+        return noise_amd::launch_aead_records(true, cs->t.keys, cs->t.nsess, priv, nrec, d_in, d_out,
+                                              d_ad, d_status, st, len_sum);
+      });
+}
+
+int noise_gpu_cswin_decrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess,
+                                     const uint64_t *d_nonces, const uint8_t *d_in,
+                                     uint64_t in_stride, uint8_t *d_out, uint64_t out_stride,
+                                     uint32_t len, uint8_t *d_status, uint64_t nrec, void *stream) {
+  if (nrec > kCsMaxRec) return arg_fail("more than 2^31 records in one batch");
+  if (!cs) return arg_fail("null table");
+  if (nrec == 0) return NOISE_GPU_OK;
+  if (!d_sess || (reinterpret_cast<uintptr_t>(d_sess) & 3u))
+    return arg_fail("null or unaligned session array");
+  if (!d_nonces || (reinterpret_cast<uintptr_t>(d_nonces) & 7u))
+    return arg_fail("null or unaligned nonce array");
+  int rc = check_uniform(true, d_in, in_stride, d_out, out_stride, len, nullptr, 0, d_status, nrec);
+  if (rc) return rc;
+  if (!noise_amd::sessions_supported(len, d_in, in_stride, d_out, out_stride))
+    return arg_fail("sessions batches need a tile length and 16-byte aligned buffers/strides "
+                    "(see noise_gpu_encrypt_sessions)");
+  if ((rc = check_device())) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(cs_window_rows(cs, st));
+  // scratch: the commit's | the prefilter's verdicts | a private copy of the
+  // index, in which a refused record carries an out-of-range value
+  const size_t commit_bytes = align16(noise_amd::cw_commit_scratch_bytes(nrec));
+  const size_t pre_bytes = align16(nrec);
+  HIP_TRY(cs_scratch(cs, commit_bytes + pre_bytes + 4 * nrec, st));
+  uint8_t *idx = static_cast<uint8_t *>(cs->scratch) + commit_bytes + pre_bytes;
+  HIP_TRY(hipMemcpyAsync(idx, d_sess, 4 * nrec, hipMemcpyDeviceToDevice, st));
+  const noise_amd::CwBatch b{reinterpret_cast<const uint8_t *>(d_sess), 4,
+                             reinterpret_cast<const uint8_t *>(d_nonces), 8, nrec};
+  return cs_window_decrypt(cs, b, commit_bytes, idx, 4, nullptr, d_out, out_stride, len, d_status, st, [&] {
+    return noise_amd::launch_aead_sessions(true, cs->t.keys, cs->t.nsess,
+                                           reinterpret_cast<const uint32_t *>(idx), d_nonces, d_in,
+                                           in_stride, d_out, out_stride, len, d_status, nrec, st);
+  });
 }
 
 int noise_gpu_x25519(const uint8_t *d_scalars, const uint8_t *d_points,

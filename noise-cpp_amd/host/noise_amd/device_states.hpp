@@ -18,6 +18,7 @@
 #include <utility>
 
 #include "noise_amd/cipher_state.hpp"
+#include "noise_amd/replay_window.hpp"
 #include "noise_gpu.h"
 
 namespace noise {
@@ -119,6 +120,62 @@ class DeviceCipherStates {
     check(noise_gpu_cs_decrypt_sessions(cs_, d_sess, d_in, in_stride, d_out, out_stride, len, d_status,
                                         nrec, stream),
           "noise_gpu_cs_decrypt_sessions");
+  }
+
+  // ---- out-of-order receive: a replay window per session (noise_gpu_cswin_*;
+  // the rule is ReplayWindow's) -------------------------------------------
+  void window_reset(std::uint64_t first, std::uint64_t count, void *stream = nullptr) {
+    check(noise_gpu_cswin_reset(cs_, first, count, stream), "noise_gpu_cswin_reset");
+  }
+  // d_status[i]: BAD_KEY / NONCE / REPLAY against the windows as they are, else OK
+  void window_filter(const std::uint32_t *d_sess, const std::uint64_t *d_nonce, std::uint8_t *d_status,
+                     std::uint64_t nrec, void *stream = nullptr) {
+    check(noise_gpu_cswin_filter(cs_, reinterpret_cast<const std::uint8_t *>(d_sess), 4,
+                                 reinterpret_cast<const std::uint8_t *>(d_nonce), 8, d_status, nrec, stream),
+          "noise_gpu_cswin_filter");
+  }
+  // d_status[i] == REC_OK marks a verified record; the losers become REC_REPLAY
+  void window_commit(const std::uint32_t *d_sess, const std::uint64_t *d_nonce, std::uint8_t *d_status,
+                     std::uint64_t nrec, void *stream = nullptr) {
+    check(noise_gpu_cswin_commit(cs_, reinterpret_cast<const std::uint8_t *>(d_sess), 4,
+                                 reinterpret_cast<const std::uint8_t *>(d_nonce), 8, d_status, nrec, stream),
+          "noise_gpu_cswin_commit");
+  }
+  // descriptors: key_idx is the session, nonce the wire's
+  void decrypt_records_window(const noise_gpu_record *d_recs, std::uint64_t nrec, const std::uint8_t *d_in,
+                              std::uint8_t *d_out, const std::uint8_t *d_ad, std::uint8_t *d_status,
+                              std::uint64_t len_sum = 0, void *stream = nullptr) {
+    check(noise_gpu_cswin_decrypt_records(cs_, d_recs, nrec, d_in, d_out, d_ad, d_status, len_sum, stream),
+          "noise_gpu_cswin_decrypt_records");
+  }
+  void decrypt_sessions_window(const std::uint32_t *d_sess, const std::uint64_t *d_nonces,
+                               const std::uint8_t *d_in, std::uint64_t in_stride, std::uint8_t *d_out,
+                               std::uint64_t out_stride, std::uint32_t len, std::uint8_t *d_status,
+                               std::uint64_t nrec, void *stream = nullptr) {
+    check(noise_gpu_cswin_decrypt_sessions(cs_, d_sess, d_nonces, d_in, in_stride, d_out, out_stride, len,
+                                           d_status, nrec, stream),
+          "noise_gpu_cswin_decrypt_sessions");
+  }
+  // A host ReplayWindow continuing session s's (migration, like state(s)).
+  // Synchronises `stream`.
+  [[nodiscard]] ReplayWindow window(std::uint64_t s, void *stream = nullptr) const {
+    struct Row {
+      std::uint64_t next;
+      std::array<std::uint32_t, 32> bits;
+    };
+    std::uint8_t *d = nullptr;
+    hip(hipMalloc(reinterpret_cast<void **>(&d), sizeof(Row)), "hipMalloc");
+    Row row{};
+    int rc = noise_gpu_cswin_get(cs_, s, 1, reinterpret_cast<std::uint64_t *>(d), d + 8, stream);
+    hipError_t e = hipSuccess;
+    if (rc == NOISE_GPU_OK) {
+      e = hipMemcpyAsync(&row, d, sizeof(Row), hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream));
+      if (e == hipSuccess) e = hipStreamSynchronize(static_cast<hipStream_t>(stream));
+    }
+    (void)hipFree(d);
+    check(rc, "noise_gpu_cswin_get");
+    hip(e, "copy of a session's window");
+    return ReplayWindow(row.next, row.bits);
   }
 
  private:

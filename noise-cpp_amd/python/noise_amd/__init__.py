@@ -19,6 +19,8 @@ HEADER = os.path.join(ROOT, "include", "noise_gpu.h")
 
 OK, E_NONCE, E_MAC, E_ARG, E_HIP, E_NODEV = 0, 1, 2, 3, 4, 5
 REC_OK, REC_BAD_MAC, REC_BAD_KEY, REC_NONCE = 0, 1, 2, 3
+REC_REPLAY = 4
+CS_WINDOW = 1024  # nonces per session's replay window (NOISE_GPU_CS_WINDOW)
 NONCE_LIMIT = (1 << 64) - 2  # noise.cpp:398 refuses n == 2^64-2
 
 
@@ -166,6 +168,13 @@ def load(path=LIB_PATH):
                                                          vp]),
         "noise_gpu_cs_decrypt_sessions": (ctypes.c_int, [vp, u8p, u8p, u64, u8p, u64, u32, u8p, u64,
                                                          vp]),
+        "noise_gpu_cswin_reset": (ctypes.c_int, [vp, u64, u64, vp]),
+        "noise_gpu_cswin_get": (ctypes.c_int, [vp, u64, u64, u8p, u8p, vp]),
+        "noise_gpu_cswin_filter": (ctypes.c_int, [vp, u8p, u64, u8p, u64, u8p, u64, vp]),
+        "noise_gpu_cswin_commit": (ctypes.c_int, [vp, u8p, u64, u8p, u64, u8p, u64, vp]),
+        "noise_gpu_cswin_decrypt_records": (ctypes.c_int, [vp, u8p, u64, u8p, u8p, u8p, u8p, u64, vp]),
+        "noise_gpu_cswin_decrypt_sessions": (ctypes.c_int, [vp, u8p, u8p, u8p, u64, u8p, u64, u32, u8p,
+                                                            u64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -399,6 +408,48 @@ class CipherStateTable:
         _check(self.lib.noise_gpu_cs_decrypt_sessions(
             self.h, _ptr(d_sess), _ptr(d_in), in_stride, _ptr(d_out), out_stride, length,
             _ptr(d_status), nrec, _stream(stream)), "noise_gpu_cs_decrypt_sessions")
+
+    # ---- out-of-order receive: a replay window per session (noise_gpu_cswin_*)
+    def window_reset(self, first, count, stream=None):
+        _check(self.lib.noise_gpu_cswin_reset(self.h, first, count, _stream(stream)),
+               "noise_gpu_cswin_reset")
+
+    def window_get(self, first, count, d_next=None, d_bits=None, stream=None):
+        """d_next: int64 tensor of count; d_bits: uint8 tensor of count 128-byte rows."""
+        _check(self.lib.noise_gpu_cswin_get(self.h, first, count, _ptr(d_next), _ptr(d_bits),
+                                            _stream(stream)), "noise_gpu_cswin_get")
+
+    def _window_primitive(self, fn, name, d_sess, d_nonce, d_status, nrec, sess_stride, nonce_stride,
+                          sess_offset, nonce_offset, stream):
+        _check(fn(self.h, ctypes.c_void_p(d_sess.data_ptr() + sess_offset), sess_stride,
+                  ctypes.c_void_p(d_nonce.data_ptr() + nonce_offset), nonce_stride, _ptr(d_status),
+                  nrec, _stream(stream)), name)
+
+    def window_filter(self, d_sess, d_nonce, d_status, nrec, sess_stride=4, nonce_stride=8,
+                      sess_offset=0, nonce_offset=0, stream=None):
+        """Addressing as assign(); read-only on the table."""
+        self._window_primitive(self.lib.noise_gpu_cswin_filter, "noise_gpu_cswin_filter", d_sess,
+                               d_nonce, d_status, nrec, sess_stride, nonce_stride, sess_offset,
+                               nonce_offset, stream)
+
+    def window_commit(self, d_sess, d_nonce, d_status, nrec, sess_stride=4, nonce_stride=8,
+                      sess_offset=0, nonce_offset=0, stream=None):
+        """d_status: REC_OK marks a verified record; the losers become REC_REPLAY."""
+        self._window_primitive(self.lib.noise_gpu_cswin_commit, "noise_gpu_cswin_commit", d_sess,
+                               d_nonce, d_status, nrec, sess_stride, nonce_stride, sess_offset,
+                               nonce_offset, stream)
+
+    def decrypt_records_window(self, d_recs, nrec, d_in, d_out, d_status, d_ad=None, len_sum=0,
+                               stream=None):
+        _check(self.lib.noise_gpu_cswin_decrypt_records(
+            self.h, _ptr(d_recs), nrec, _ptr(d_in), _ptr(d_out), _ptr(d_ad), _ptr(d_status), len_sum,
+            _stream(stream)), "noise_gpu_cswin_decrypt_records")
+
+    def decrypt_sessions_window(self, d_sess, d_nonces, d_in, in_stride, d_out, out_stride, length,
+                                d_status, nrec, stream=None):
+        _check(self.lib.noise_gpu_cswin_decrypt_sessions(
+            self.h, _ptr(d_sess), _ptr(d_nonces), _ptr(d_in), in_stride, _ptr(d_out), out_stride, length,
+            _ptr(d_status), nrec, _stream(stream)), "noise_gpu_cswin_decrypt_sessions")
 
 
 # ---- host-buffer entry points (CipherState single-record path) ------------

@@ -300,6 +300,9 @@ inline uint32_t __umul24(uint32_t a, uint32_t b) { return (a & 0xffffffu) * (b &
 inline unsigned long long atomicAdd(unsigned long long *p, unsigned long long v) {
   return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST);
 }
+inline unsigned int atomicOr(unsigned int *p, unsigned int v) {
+  return __atomic_fetch_or(p, v, __ATOMIC_SEQ_CST);
+}
 inline unsigned long long atomicMin(unsigned long long *p, unsigned long long v) {
   unsigned long long old = __atomic_load_n(p, __ATOMIC_SEQ_CST);
   while (v < old && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_SEQ_CST,
