@@ -315,6 +315,12 @@ __device__ __forceinline__ void from26(const F26 &f, uint32_t &h0, uint32_t &h1,
 }
 
 // full carry propagation modulo 2^130-5 (limbs < 2^31 in, < 2^26(+1) out)
+// One call leaves a[0], a[2], a[3], a[4] < 2^26 and a[1] <= 2^26, a value below
+// 2^130 + 2^26 < 2p: from26 then gives h4 <= 4, which is what poly_final's
+// single subtraction needs.  A second call only moves a[1]'s bit 26 into a[2]
+// and from26 returns the same h, so the endings that carry twice before from26
+// (single_kernels.hip, k_seg_finalize_w, the segment sums) would be as right
+// with one; tools/emu/emu_poly_edges.cpp runs them on h >= p both ways.
 __device__ __forceinline__ void carry26(F26 &f) {
   uint32_t c;
   c = f.a[0] >> 26; f.a[0] &= kM26; f.a[1] += c;

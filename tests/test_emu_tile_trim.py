@@ -13,6 +13,12 @@
   before from26, with the device functions alone under ASan + UBSan: r with
   every clamped bit set over all-ones blocks, and 10,000 random (r, message)
   pairs, against a straight Horner chain; no limb reaches 2^31.
+  What it does not prove: the chain it compares with is the kernel's own
+  poly_block / poly_final, so an error in those two cancels, and under random
+  (r, message) the accumulator never lies in p <= h < 2^130 on entry to
+  poly_final nor is a lane sum ever held as p + T.  tests/test_poly_edges.py
+  (tools/emu/emu_poly_edges) feeds chosen residues and compares with tags
+  computed in Python.
 Test infrastructure only: the product runs these kernels on the GPU."""
 import os
 import subprocess
