@@ -1,0 +1,407 @@
+// cstate_api.hip -- the noise_gpu_cs_* / noise_gpu_cswin_* C ABI
+// (include/noise_gpu.h): device-resident CipherState tables.  What is here:
+// the table's memory, the argument checks and the grow-only scratch; the
+// sequences of launches behind the composite calls are cstate_calls.hpp's,
+// the kernels cstate_kernels.hip's and cswin_kernels.hip's.  No kernels here.
+#include <hip/hip_runtime.h>
+
+#include <new>
+
+#include "cstate_calls.hpp"
+#include "noise_amd/dev_mem.hpp"
+
+using namespace noise_amd;
+
+// nsess x (key row, counter n, rank scratch) and the batch scratch, in HBM on
+// the device current at create
+struct noise_gpu_cs {
+  CsTableView t{};
+  CsWindowView w{};  // replay windows: allocated by the first windowed call
+  uint8_t *scratch = nullptr;  // grow-only; laid out per call by cs_scratch_layout
+  size_t scratch_size = 0;
+};
+
+namespace {
+
+#define CS_TRY(expr)                                          \
+  do {                                                        \
+    hipError_t e_ = (expr);                                   \
+    if (e_ != hipSuccess) return api_hip_fail(e_, #expr);     \
+  } while (0)
+
+constexpr uint64_t kCsMaxSess = 0xfffffffeull;  // 2^32-2: 0xffffffff marks a refused record
+constexpr uint64_t kCsMaxRec = 1ull << 31;
+constexpr uint64_t kCsWinRow = NOISE_GPU_CS_WINDOW / 8;  // bytes of a session's bitmap
+
+// ---- the table's device arrays: the one list create, the window rows and
+// destroy go by.  The rows come from hipMalloc at create; the windows and the
+// scratch are stream-ordered (dev_mem.hpp).
+struct CsArray {
+  void **p;
+  size_t bytes;
+  bool pooled;
+};
+enum : int { kCsRows = 0, kCsWindows = 3, kCsScratch = 5, kCsArrays = 6 };
+CsArray cs_array(noise_gpu_cs *cs, int i) {
+  const size_t n = cs->t.nsess;
+  const CsArray list[kCsArrays] = {
+      {reinterpret_cast<void **>(&cs->t.keys), 32 * n, false},
+      {reinterpret_cast<void **>(&cs->t.ctr), 8 * n, false},
+      {reinterpret_cast<void **>(&cs->t.start), 4 * n, false},
+      {reinterpret_cast<void **>(&cs->w.next), 8 * n, true},
+      {reinterpret_cast<void **>(&cs->w.bits), kCsWinRow * n, true},
+      {reinterpret_cast<void **>(&cs->scratch), cs->scratch_size, true}};
+  return list[i];
+}
+
+// arrays [from, to): allocated (on `st` where stream-ordered) and zeroed
+hipError_t cs_arrays_alloc(noise_gpu_cs *cs, int from, int to, hipStream_t st) {
+  for (int i = from; i < to; ++i) {
+    const CsArray a = cs_array(cs, i);
+    hipError_t e = a.pooled ? dev_alloc(a.p, a.bytes, st) : hipMalloc(a.p, a.bytes);
+    if (e == hipSuccess) e = a.pooled ? hipMemsetAsync(*a.p, 0, a.bytes, st) : hipMemset(*a.p, 0, a.bytes);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// those of arrays [from, to) that exist: wiped, then freed (after the work
+// queued on `st` where stream-ordered); the last failure is returned
+hipError_t cs_arrays_drop(noise_gpu_cs *cs, int from, int to, hipStream_t st) {
+  hipError_t rc = hipSuccess;
+  auto keep = [&rc](hipError_t e) {
+    if (e != hipSuccess) rc = e;
+  };
+  for (int i = from; i < to; ++i) {
+    const CsArray a = cs_array(cs, i);
+    if (!*a.p) continue;
+    if (a.pooled) {
+      keep(dev_wipe_free(*a.p, a.bytes, st));
+    } else {
+      keep(hipMemset(*a.p, 0, a.bytes));
+      keep(hipFree(*a.p));
+    }
+    *a.p = nullptr;
+  }
+  return rc;
+}
+
+// the table's scratch, >= bytes; the smaller one is wiped and freed
+// stream-ordered after the launches that still use it
+hipError_t cs_scratch(noise_gpu_cs *cs, size_t bytes, hipStream_t st) {
+  if (bytes <= cs->scratch_size) return hipSuccess;
+  hipError_t e = cs_arrays_drop(cs, kCsScratch, kCsArrays, st);
+  cs->scratch_size = 0;
+  if (e != hipSuccess) return e;
+  if ((e = dev_alloc(reinterpret_cast<void **>(&cs->scratch), bytes, st)) != hipSuccess) return e;
+  cs->scratch_size = bytes;
+  return hipSuccess;
+}
+
+// a composite call's end
+int cs_done(hipError_t e) { return e == hipSuccess ? NOISE_GPU_OK : api_hip_fail(e, "CipherState table call"); }
+
+hipError_t cs_window_clear(noise_gpu_cs *cs, uint64_t first, uint64_t count, hipStream_t st) {
+  if (count == 0) return hipSuccess;
+  hipError_t e = hipMemsetAsync(cs->w.next + first, 0, 8 * count, st);
+  if (e != hipSuccess) return e;
+  return hipMemsetAsync(reinterpret_cast<uint8_t *>(cs->w.bits) + kCsWinRow * first, 0,
+                        kCsWinRow * count, st);
+}
+
+// the window rows, fresh on the first call
+hipError_t cs_window_rows(noise_gpu_cs *cs, hipStream_t st) {
+  if (cs->w.next) return hipSuccess;
+  const hipError_t e = cs_arrays_alloc(cs, kCsWindows, kCsScratch, st);
+  if (e != hipSuccess) (void)cs_arrays_drop(cs, kCsWindows, kCsScratch, st);
+  return e;
+}
+
+// ---- argument checks ----
+int cs_check_range(const noise_gpu_cs *cs, uint64_t first, uint64_t count) {
+  if (first + count < first) return api_arg_fail("first + count overflows");
+  if (!cs) return api_arg_fail("null table");
+  if (first + count > cs->t.nsess) return api_arg_fail("sessions [first, first + count) outside the table");
+  return NOISE_GPU_OK;
+}
+
+int cs_check_assign(const noise_gpu_cs *cs, const void *d_sess, uint64_t sess_stride,
+                    const void *d_nonce, uint64_t nonce_stride, uint64_t nrec) {
+  if (sess_stride == 0 || (sess_stride & 3u)) return api_arg_fail("session stride must be a non-zero multiple of 4");
+  if (nonce_stride == 0 || (nonce_stride & 7u)) return api_arg_fail("nonce stride must be a non-zero multiple of 8");
+  if (nrec > kCsMaxRec) return api_arg_fail("more than 2^31 records in one batch");
+  if (!cs) return api_arg_fail("null table");
+  if (nrec == 0) return NOISE_GPU_OK;
+  if (!d_sess || !d_nonce) return api_arg_fail("null session / nonce array");
+  if ((reinterpret_cast<uintptr_t>(d_sess) & 3u) || (reinterpret_cast<uintptr_t>(d_nonce) & 7u))
+    return api_arg_fail("session / nonce arrays must be 4 / 8-byte aligned");
+  return NOISE_GPU_OK;
+}
+
+// The composite calls' checks end with the device's.  OK with nrec == 0:
+// nothing to do.
+int cs_check_records(const noise_gpu_cs *cs, bool decrypt, const void *d_recs, uint64_t nrec,
+                     const void *d_in, const void *d_out, const void *d_status) {
+  if (nrec > kCsMaxRec) return api_arg_fail("more than 2^31 records in one batch");
+  if (!cs) return api_arg_fail("null table");
+  if (nrec == 0) return NOISE_GPU_OK;
+  if (!d_recs || !d_in || !d_out || (decrypt && !d_status))
+    return api_arg_fail(decrypt ? "null descriptors / buffers / status" : "null descriptors / buffers");
+  if (reinterpret_cast<uintptr_t>(d_recs) & 7u) return api_arg_fail("descriptors must be 8-byte aligned");
+  return api_check_device();
+}
+
+// windowed: the caller's nonce array is checked too
+int cs_check_sessions(const noise_gpu_cs *cs, bool decrypt, bool windowed, const uint32_t *d_sess,
+                      const uint64_t *d_nonces, const uint8_t *d_in, uint64_t in_stride,
+                      const uint8_t *d_out, uint64_t out_stride, uint32_t len, const uint8_t *d_status,
+                      uint64_t nrec) {
+  if (nrec > kCsMaxRec) return api_arg_fail("more than 2^31 records in one batch");
+  if (!cs) return api_arg_fail("null table");
+  if (nrec == 0) return NOISE_GPU_OK;
+  if (!d_sess || (reinterpret_cast<uintptr_t>(d_sess) & 3u))
+    return api_arg_fail("null or unaligned session array");
+  if (windowed && (!d_nonces || (reinterpret_cast<uintptr_t>(d_nonces) & 7u)))
+    return api_arg_fail("null or unaligned nonce array");
+  const int rc = api_check_uniform(decrypt, d_in, in_stride, d_out, out_stride, len, nullptr, 0, d_status, nrec);
+  if (rc) return rc;
+  if (!sessions_supported(len, d_in, in_stride, d_out, out_stride))
+    return api_arg_fail("sessions batches need a tile length and 16-byte aligned buffers/strides "
+                        "(see noise_gpu_encrypt_sessions)");
+  return api_check_device();
+}
+
+// ---- the composite calls: checks, scratch, then cstate_calls.hpp ----
+int cs_records(bool decrypt, noise_gpu_cs *cs, noise_gpu_record *d_recs, uint64_t nrec,
+               const uint8_t *d_in, uint8_t *d_out, const uint8_t *d_ad, uint8_t *d_status,
+               uint64_t len_sum, void *stream) {
+  const int rc = cs_check_records(cs, decrypt, d_recs, nrec, d_in, d_out, d_status);
+  if (rc || nrec == 0) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  CS_TRY(cs_scratch(cs, cs_scratch_layout(false, true, nrec).total, st));
+  return cs_done(cs_inorder_call(
+      decrypt, cs->t, cs_columns(d_recs), nrec, cs->scratch, d_status, st, [&](const CsColumns &mine) {
+        return launch_aead_records(decrypt, cs->t.keys, cs->t.nsess, mine.recs, nrec, d_in, d_out, d_ad,
+                                   decrypt ? d_status : nullptr, st, len_sum);
+      }));
+}
+
+int cs_sessions(bool decrypt, noise_gpu_cs *cs, const uint32_t *d_sess, const uint8_t *d_in,
+                uint64_t in_stride, uint8_t *d_out, uint64_t out_stride, uint32_t len,
+                uint8_t *d_status, uint64_t nrec, void *stream) {
+  const int rc = cs_check_sessions(cs, decrypt, false, d_sess, nullptr, d_in, in_stride, d_out, out_stride,
+                                   len, d_status, nrec);
+  if (rc || nrec == 0) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  CS_TRY(cs_scratch(cs, cs_scratch_layout(false, false, nrec).total, st));
+  return cs_done(cs_inorder_call(
+      decrypt, cs->t, cs_columns(d_sess, nullptr), nrec, cs->scratch, d_status, st, [&](const CsColumns &mine) {
+        return launch_aead_sessions(decrypt, cs->t.keys, cs->t.nsess, reinterpret_cast<const uint32_t *>(mine.sess),
+                                    reinterpret_cast<const uint64_t *>(mine.nonce), d_in, in_stride, d_out,
+                                    out_stride, len, decrypt ? d_status : nullptr, nrec, st);
+      }));
+}
+
+}  // namespace
+
+extern "C" {
+
+int noise_gpu_cs_create(uint64_t nsess, noise_gpu_cs **out) {
+  if (!out) return api_arg_fail("null output");
+  *out = nullptr;
+  if (nsess == 0 || nsess > kCsMaxSess) return api_arg_fail("a CipherState table holds 1 .. 2^32-2 sessions");
+  int rc = api_check_device();
+  if (rc) return rc;
+  noise_gpu_cs *cs = new (std::nothrow) noise_gpu_cs();
+  if (!cs) return api_arg_fail("out of host memory");
+  cs->t.nsess = (uint32_t)nsess;
+  hipError_t e = cs_arrays_alloc(cs, kCsRows, kCsWindows, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    (void)cs_arrays_drop(cs, kCsRows, kCsWindows, nullptr);
+    delete cs;
+    return api_hip_fail(e, "CipherState table allocation");
+  }
+  *out = cs;
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cs_destroy(noise_gpu_cs *cs) {
+  if (!cs) return NOISE_GPU_OK;
+  // before: the table's last calls, whatever stream they ran on; after: the wipes
+  hipError_t e = hipSuccess;
+  for (hipError_t step :
+       {hipDeviceSynchronize(), cs_arrays_drop(cs, kCsRows, kCsArrays, nullptr), hipDeviceSynchronize()})
+    if (step != hipSuccess) e = step;
+  delete cs;
+  return e == hipSuccess ? NOISE_GPU_OK : api_hip_fail(e, "noise_gpu_cs_destroy");
+}
+
+int noise_gpu_cs_set(noise_gpu_cs *cs, uint64_t first, uint64_t count, const uint8_t *d_keys,
+                     uint64_t key_stride, const uint64_t *d_n, void *stream) {
+  if (d_keys && key_stride < 32) return api_arg_fail("key rows are 32 bytes: key_stride >= 32");
+  if (reinterpret_cast<uintptr_t>(d_n) & 7u) return api_arg_fail("counters must be 8-byte aligned");
+  int rc = cs_check_range(cs, first, count);
+  if (rc || count == 0) return rc;
+  if (!d_keys && !d_n) return api_arg_fail("neither key rows nor counters given");
+  if ((rc = api_check_device())) return rc;
+  CS_TRY(launch_cs_set(cs->t, first, count, d_keys, key_stride, d_n, (hipStream_t)stream));
+  // a new key starts a new nonce space
+  if (d_keys && cs->w.next) CS_TRY(cs_window_clear(cs, first, count, (hipStream_t)stream));
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cs_get(const noise_gpu_cs *cs, uint64_t first, uint64_t count, uint8_t *d_keys,
+                     uint64_t *d_n, void *stream) {
+  int rc = cs_check_range(cs, first, count);
+  if (rc || count == 0) return rc;
+  if ((rc = api_check_device())) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  if (d_keys)
+    CS_TRY(hipMemcpyAsync(d_keys, cs->t.keys + 32 * first, 32 * count, hipMemcpyDeviceToDevice, st));
+  if (d_n) CS_TRY(hipMemcpyAsync(d_n, cs->t.ctr + first, 8 * count, hipMemcpyDeviceToDevice, st));
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cs_rekey(noise_gpu_cs *cs, const uint32_t *d_sess, uint64_t count, void *stream) {
+  if (reinterpret_cast<uintptr_t>(d_sess) & 3u) return api_arg_fail("session array must be 4-byte aligned");
+  if (!cs) return api_arg_fail("null table");
+  if (!d_sess) count = cs->t.nsess;
+  if (count == 0) return NOISE_GPU_OK;
+  int rc = api_check_device();
+  if (rc) return rc;
+  CS_TRY(launch_cs_rekey(cs->t, d_sess, count, (hipStream_t)stream));
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cs_assign(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t sess_stride,
+                        uint8_t *d_nonce, uint64_t nonce_stride, uint8_t *d_status, uint64_t nrec,
+                        void *stream) {
+  int rc = cs_check_assign(cs, d_sess, sess_stride, d_nonce, nonce_stride, nrec);
+  if (rc || nrec == 0) return rc;
+  if ((rc = api_check_device())) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  CS_TRY(cs_scratch(cs, cs_assign_scratch_bytes(nrec), st));
+  const CsAssign a{d_sess, sess_stride, d_nonce, nonce_stride, nullptr, 0, nullptr, 0, d_status, nrec};
+  CS_TRY(launch_cs_assign(cs->t, a, cs->scratch, st));
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cs_encrypt_records(noise_gpu_cs *cs, noise_gpu_record *d_recs, uint64_t nrec,
+                                 const uint8_t *d_in, uint8_t *d_out, const uint8_t *d_ad,
+                                 uint8_t *d_status, uint64_t len_sum, void *stream) {
+  return cs_records(false, cs, d_recs, nrec, d_in, d_out, d_ad, d_status, len_sum, stream);
+}
+
+int noise_gpu_cs_decrypt_records(noise_gpu_cs *cs, noise_gpu_record *d_recs, uint64_t nrec,
+                                 const uint8_t *d_in, uint8_t *d_out, const uint8_t *d_ad,
+                                 uint8_t *d_status, uint64_t len_sum, void *stream) {
+  return cs_records(true, cs, d_recs, nrec, d_in, d_out, d_ad, d_status, len_sum, stream);
+}
+
+int noise_gpu_cs_encrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess, const uint8_t *d_in,
+                                  uint64_t in_stride, uint8_t *d_out, uint64_t out_stride,
+                                  uint32_t len, uint8_t *d_status, uint64_t nrec, void *stream) {
+  return cs_sessions(false, cs, d_sess, d_in, in_stride, d_out, out_stride, len, d_status, nrec, stream);
+}
+
+int noise_gpu_cs_decrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess, const uint8_t *d_in,
+                                  uint64_t in_stride, uint8_t *d_out, uint64_t out_stride,
+                                  uint32_t len, uint8_t *d_status, uint64_t nrec, void *stream) {
+  return cs_sessions(true, cs, d_sess, d_in, in_stride, d_out, out_stride, len, d_status, nrec, stream);
+}
+
+int noise_gpu_cswin_reset(noise_gpu_cs *cs, uint64_t first, uint64_t count, void *stream) {
+  int rc = cs_check_range(cs, first, count);
+  if (rc || count == 0) return rc;
+  if ((rc = api_check_device())) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  const bool fresh = !cs->w.next;
+  CS_TRY(cs_window_rows(cs, st));
+  if (!fresh) CS_TRY(cs_window_clear(cs, first, count, st));
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cswin_get(const noise_gpu_cs *cs, uint64_t first, uint64_t count, uint64_t *d_next,
+                        uint8_t *d_bits, void *stream) {
+  if (reinterpret_cast<uintptr_t>(d_next) & 7u) return api_arg_fail("next array must be 8-byte aligned");
+  int rc = cs_check_range(cs, first, count);
+  if (rc || count == 0) return rc;
+  if ((rc = api_check_device())) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  if (!cs->w.next) {  // never used a window: the fresh state
+    if (d_next) CS_TRY(hipMemsetAsync(d_next, 0, 8 * count, st));
+    if (d_bits) CS_TRY(hipMemsetAsync(d_bits, 0, kCsWinRow * count, st));
+    return NOISE_GPU_OK;
+  }
+  if (d_next)
+    CS_TRY(hipMemcpyAsync(d_next, cs->w.next + first, 8 * count, hipMemcpyDeviceToDevice, st));
+  if (d_bits)
+    CS_TRY(hipMemcpyAsync(d_bits, reinterpret_cast<const uint8_t *>(cs->w.bits) + kCsWinRow * first,
+                          kCsWinRow * count, hipMemcpyDeviceToDevice, st));
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cswin_filter(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t sess_stride,
+                           const uint8_t *d_nonce, uint64_t nonce_stride, uint8_t *d_status,
+                           uint64_t nrec, void *stream) {
+  int rc = cs_check_assign(cs, d_sess, sess_stride, d_nonce, nonce_stride, nrec);
+  if (rc || nrec == 0) return rc;
+  if (!d_status) return api_arg_fail("null status buffer");
+  if ((rc = api_check_device())) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  CS_TRY(cs_window_rows(cs, st));
+  const CwBatch b{d_sess, sess_stride, d_nonce, nonce_stride, nrec};
+  CS_TRY(launch_cw_filter(cs->t, cs->w, b, d_status, nullptr, 0, st));
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cswin_commit(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t sess_stride,
+                           const uint8_t *d_nonce, uint64_t nonce_stride, uint8_t *d_status,
+                           uint64_t nrec, void *stream) {
+  int rc = cs_check_assign(cs, d_sess, sess_stride, d_nonce, nonce_stride, nrec);
+  if (rc || nrec == 0) return rc;
+  if (!d_status) return api_arg_fail("null status buffer");
+  if ((rc = api_check_device())) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  CS_TRY(cs_window_rows(cs, st));
+  CS_TRY(cs_scratch(cs, cw_commit_scratch_bytes(nrec), st));
+  const CwBatch b{d_sess, sess_stride, d_nonce, nonce_stride, nrec};
+  CS_TRY(launch_cw_commit(cs->t, cs->w, b, d_status, cs->scratch, st));
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_cswin_decrypt_records(noise_gpu_cs *cs, const noise_gpu_record *d_recs, uint64_t nrec,
+                                    const uint8_t *d_in, uint8_t *d_out, const uint8_t *d_ad,
+                                    uint8_t *d_status, uint64_t len_sum, void *stream) {
+  const int rc = cs_check_records(cs, true, d_recs, nrec, d_in, d_out, d_status);
+  if (rc || nrec == 0) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  CS_TRY(cs_window_rows(cs, st));
+  CS_TRY(cs_scratch(cs, cs_scratch_layout(true, true, nrec).total, st));
+  return cs_done(cs_window_call(
+      cs->t, cs->w, cs_columns(d_recs), nrec, cs->scratch, d_out, 0, 0, d_status, st, [&](const CsColumns &mine) {
+        return launch_aead_records(true, cs->t.keys, cs->t.nsess, mine.recs, nrec, d_in, d_out, d_ad, d_status, st,
+                                   len_sum);
+      }));
+}
+
+int noise_gpu_cswin_decrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess,
+                                     const uint64_t *d_nonces, const uint8_t *d_in,
+                                     uint64_t in_stride, uint8_t *d_out, uint64_t out_stride,
+                                     uint32_t len, uint8_t *d_status, uint64_t nrec, void *stream) {
+  const int rc = cs_check_sessions(cs, true, true, d_sess, d_nonces, d_in, in_stride, d_out, out_stride, len,
+                                   d_status, nrec);
+  if (rc || nrec == 0) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  CS_TRY(cs_window_rows(cs, st));
+  CS_TRY(cs_scratch(cs, cs_scratch_layout(true, false, nrec).total, st));
+  return cs_done(cs_window_call(
+      cs->t, cs->w, cs_columns(d_sess, d_nonces), nrec, cs->scratch, d_out, out_stride, len, d_status, st,
+      [&](const CsColumns &mine) {
+        return launch_aead_sessions(true, cs->t.keys, cs->t.nsess, reinterpret_cast<const uint32_t *>(mine.sess),
+                                    d_nonces, d_in, in_stride, d_out, out_stride, len, d_status, nrec, st);
+      }));
+}
+
+}  // extern "C"

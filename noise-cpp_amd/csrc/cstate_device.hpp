@@ -1,6 +1,7 @@
 // cstate_device.hpp -- what the CipherState-table translation units
 // (cstate_kernels.hip, cswin_kernels.hip) share: the grid cap, the refused
-// mark and the table's row reads.
+// mark and the table's row reads; and, with records_kernels.hip, the key-row
+// test and the wave scan.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,10 +19,22 @@ inline unsigned cs_capped(uint64_t want) {
   return (unsigned)(want < NOISE_GRID_CAP ? want : NOISE_GRID_CAP);
 }
 
-__device__ __forceinline__ bool cs_key_zero(const uint8_t *keys, uint32_t s) {
-  const uint4 *kp = reinterpret_cast<const uint4 *>(keys + 32ull * s);
+// an all-zero key row is "no key" (Noise HasKey() false, e.g. the rows
+// noise_gpu_hs_split leaves for failed handshakes): never used to encrypt
+__device__ __forceinline__ bool key_row_zero(const uint8_t *keys, uint32_t ki) {
+  const uint4 *kp = reinterpret_cast<const uint4 *>(keys + 32ull * ki);
   const uint4 a = kp[0], b = kp[1];
   return (a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w) == 0u;
+}
+
+// wave-wide inclusive prefix sum (all 64 lanes participate)
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t t = (uint32_t)__shfl((int)v, (int)(lane >= (uint32_t)d ? lane - d : lane));
+    if (lane >= (uint32_t)d) v += t;
+  }
+  return v;
 }
 
 __device__ __forceinline__ uint32_t cs_sess_at(const uint8_t *sess, uint64_t stride, uint64_t i) {

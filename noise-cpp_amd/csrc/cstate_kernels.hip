@@ -71,13 +71,12 @@ struct CsScratch {
   uint32_t *part;  // [nw][256] per-wave counts, scanned in place to bases
   unsigned long long *pair[2];  // (record index << 32 | session), ping-pong
 };
-inline size_t cs_a16(size_t x) { return (x + 15) & ~size_t(15); }
 inline size_t cs_carve(CsScratch *s, uint8_t *base, uint64_t nrec) {
   const CsGeom g = cs_geom(nrec);
   size_t off = 0;
   auto take = [&](size_t bytes) {
     uint8_t *p = base ? base + off : nullptr;
-    off += cs_a16(bytes);
+    off += align16(bytes);
     return reinterpret_cast<uint32_t *>(p);
   };
   uint32_t *hdr = take(64), *tot = take(4 * kCsBins), *part = take(4ull * kCsBins * g.nw);
@@ -88,15 +87,6 @@ inline size_t cs_carve(CsScratch *s, uint8_t *base, uint64_t nrec) {
 }
 
 }  // namespace
-
-__device__ __forceinline__ uint32_t cs_incl_scan(uint32_t v, uint32_t lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t t = (uint32_t)__shfl((int)v, (int)(lane >= (uint32_t)d ? lane - d : lane));
-    if (lane >= (uint32_t)d) v += t;
-  }
-  return v;
-}
 
 // lanes below this one in mask m
 __device__ __forceinline__ uint32_t cs_below(uint64_t m) {
@@ -162,7 +152,7 @@ __global__ __launch_bounds__(64) void k_cs_small(const uint8_t *sess, uint64_t s
   bool keyless = true;
   if (valid) {
     n0 = ctr[s];
-    keyless = cs_key_zero(keys, s);
+    keyless = key_row_zero(keys, s);
   }
   __syncthreads();  // every lane has read n[s] before a tail lane moves it
   if (valid) {
@@ -234,7 +224,7 @@ __global__ __launch_bounds__(64) void k_cs_scan(uint32_t *part, uint32_t nw, uin
     for (uint32_t i = 0; i < kPer; ++i) v[i] = w0 + i < nw ? part[(uint64_t)(w0 + i) * kCsBins + d] : 0u;
 #pragma unroll
     for (uint32_t i = 0; i < kPer; ++i) sum += v[i];
-    const uint32_t inc = cs_incl_scan(sum, lane);
+    const uint32_t inc = wave_incl_scan(sum, lane);
     uint32_t run = inc - sum;
 #pragma unroll
     for (uint32_t i = 0; i < kPer; ++i) {
@@ -259,7 +249,7 @@ __global__ __launch_bounds__(64) void k_cs_scatter(const uint8_t *sess, uint64_t
     uint32_t t[4], sum = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) sum += t[k] = tot[4u * lane + k];
-    const uint32_t inc = cs_incl_scan(sum, lane);
+    const uint32_t inc = wave_incl_scan(sum, lane);
     uint32_t b = inc - sum;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -335,7 +325,7 @@ __global__ __launch_bounds__(64) void k_cs_apply(const unsigned long long *pair,
   for (uint64_t p = (uint64_t)blockIdx.x * 64 + threadIdx.x; p < n; p += (uint64_t)gridDim.x * 64) {
     const unsigned long long pr = pair[p];
     const uint32_t s = (uint32_t)pr;
-    cs_apply_one(o, (uint32_t)(pr >> 32), cs_key_zero(keys, s), ctr[s], (uint32_t)p - start[s]);
+    cs_apply_one(o, (uint32_t)(pr >> 32), key_row_zero(keys, s), ctr[s], (uint32_t)p - start[s]);
   }
 }
 
@@ -346,7 +336,7 @@ __global__ __launch_bounds__(64) void k_cs_tails(const unsigned long long *pair,
   for (uint64_t p = (uint64_t)blockIdx.x * 64 + threadIdx.x; p < n; p += (uint64_t)gridDim.x * 64) {
     const uint32_t s = (uint32_t)pair[p];
     if (p + 1 < n && (uint32_t)pair[p + 1] == s) continue;
-    if (!cs_key_zero(keys, s)) ctr[s] = cs_advance(ctr[s], (uint32_t)p - start[s] + 1u);
+    if (!key_row_zero(keys, s)) ctr[s] = cs_advance(ctr[s], (uint32_t)p - start[s] + 1u);
   }
 }
 

@@ -64,8 +64,6 @@ constexpr uint64_t kCwLimit = 0xfffffffffffffffeull;  // nonces >= 2^64-2 are re
 constexpr uint64_t kCwWindow = NOISE_GPU_CS_WINDOW;
 static_assert(NOISE_GPU_CS_WINDOW == 1024u, "32 words per row, one per lane of a half wave");
 
-inline size_t cw_a16(size_t x) { return (x + 15) & ~size_t(15); }
-
 }  // namespace
 
 __device__ __forceinline__ uint64_t cw_nonce_at(const uint8_t *nonce, uint64_t stride, uint64_t i) {
@@ -158,7 +156,7 @@ __global__ __launch_bounds__(64) void k_cw_filter(const uint8_t *sess, uint64_t 
   for (uint64_t i = (uint64_t)blockIdx.x * 64 + threadIdx.x; i < nrec; i += (uint64_t)gridDim.x * 64) {
     const uint32_t s = cs_sess_at(sess, sess_stride, i);
     uint32_t st = NOISE_GPU_REC_OK;
-    if (s >= nsess || cs_key_zero(keys, s)) {
+    if (s >= nsess || key_row_zero(keys, s)) {
       st = NOISE_GPU_REC_BAD_KEY;
     } else {
       const uint64_t n = cw_nonce_at(nonce, nonce_stride, i);
@@ -317,7 +315,7 @@ hipError_t launch_cw_filter(const CsTableView &t, const CsWindowView &w, const C
 }
 
 size_t cw_commit_scratch_bytes(uint64_t nrec) {
-  return nrec <= 64 ? 0 : cw_a16(4 * nrec) + cs_sort_scratch_bytes(nrec);
+  return nrec <= 64 ? 0 : align16(4 * nrec) + cs_sort_scratch_bytes(nrec);
 }
 
 hipError_t launch_cw_commit(const CsTableView &t, const CsWindowView &w, const CwBatch &b,
@@ -336,7 +334,7 @@ hipError_t launch_cw_commit(const CsTableView &t, const CsWindowView &w, const C
                      t.nsess, status, key, b.nrec);
   CsSorted sorted;
   const hipError_t e = launch_cs_sort(reinterpret_cast<const uint8_t *>(key), 4, t.nsess, b.nrec,
-                                      base + cw_a16(4 * b.nrec), nullptr, stream, &sorted);
+                                      base + align16(4 * b.nrec), nullptr, stream, &sorted);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_cw_commit, gr, b64, 0, stream, sorted.pair, sorted.hdr, b.nonce, b.nonce_stride,
                      w.next, w.bits, status);

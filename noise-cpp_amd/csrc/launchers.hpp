@@ -1,13 +1,17 @@
-// launchers.hpp -- internal interface between the C-ABI layer
-// (noise_gpu_api.hip) and the kernels (aead_kernels.hip).
+// launchers.hpp -- internal interface between the C-ABI translation units
+// (noise_gpu_api.hip, cstate_api.hip, handshake_batch.hip) and the kernels'
+// launchers, and the helpers those translation units share.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "noise_gpu.h"
 #include "stream_res.hpp"  // per-stream scratch and companions (records_scratch_*)
 
 namespace noise_amd {
+
+inline size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
 
 hipError_t launch_aead_uniform(bool decrypt, const uint32_t key[8],
                                uint64_t nonce0, const uint8_t *in,
@@ -270,10 +274,14 @@ hipError_t launch_cw_finish(const uint8_t *pre, uint8_t *status, const noise_gpu
                             uint8_t *out, uint64_t out_stride, uint32_t len, uint64_t nrec,
                             hipStream_t stream);
 
-// C-ABI helpers shared by the API translation units (noise_gpu_api.hip)
+// C-ABI helpers shared by the API translation units (defined in noise_gpu_api.hip)
 int api_hip_fail(hipError_t e, const char *what);
 int api_arg_fail(const char *msg);
 int api_check_device();
+// a uniform batch's buffers and strides.  enc: in = len-byte records, out = len+16
+int api_check_uniform(bool decrypt, const void *in, uint64_t in_stride, const void *out,
+                      uint64_t out_stride, uint32_t len, const void *ad, uint32_t ad_len,
+                      const void *status, uint64_t nrec);
 
 hipError_t launch_fill_synthetic(uint8_t *dst, uint64_t offset,
                                  uint64_t nbytes, uint64_t seed,

@@ -1,7 +1,10 @@
 // noise_gpu_api.hip -- the C ABI (include/noise_gpu.h) over the gfx950
 // kernels.  Argument checks, launches, and the host-buffer entry points
 // (pinned staging for single records; chunked, multi-stream pipelines for
-// host-resident batches).  Nothing here computes ChaCha20 or Poly1305:
+// host-resident batches).  The batched handshakes (noise_gpu_hs_*) are
+// handshake_batch.hip's and the CipherState tables (noise_gpu_cs_*,
+// noise_gpu_cswin_*) cstate_api.hip's; they report through the api_* helpers
+// defined here (launchers.hpp).  Nothing here computes ChaCha20 or Poly1305:
 // every record goes through the HIP kernels, and without a gfx950 device
 // every entry point fails with NOISE_GPU_E_NODEV / NOISE_GPU_E_HIP.
 #include <hip/hip_runtime.h>
@@ -608,7 +611,7 @@ int one_record(bool dec, const uint8_t key[32], uint64_t nonce, const uint8_t *a
   return rc;
 }
 
-inline size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
+using noise_amd::align16;
 
 }  // namespace
 
@@ -616,6 +619,11 @@ namespace noise_amd {
 int api_hip_fail(hipError_t e, const char *what) { return hip_fail(e, what); }
 int api_arg_fail(const char *msg) { return arg_fail(msg); }
 int api_check_device() { return check_device(); }
+int api_check_uniform(bool decrypt, const void *in, uint64_t in_stride, const void *out,
+                      uint64_t out_stride, uint32_t len, const void *ad, uint32_t ad_len,
+                      const void *status, uint64_t nrec) {
+  return check_uniform(decrypt, in, in_stride, out, out_stride, len, ad, ad_len, status, nrec);
+}
 }  // namespace noise_amd
 
 extern "C" {
@@ -787,420 +795,6 @@ int noise_gpu_rekey_keys(uint8_t *d_keys, uint64_t nkeys, void *stream) {
   if (rc) return rc;
   HIP_TRY(noise_amd::launch_rekey(d_keys, nkeys, (hipStream_t)stream));
   return NOISE_GPU_OK;
-}
-
-// ---- device-resident CipherState tables ------------------------------------
-}  // extern "C"
-
-// nsess x (key row, counter n, rank scratch) and the batch scratch, in HBM on
-// the device current at create
-struct noise_gpu_cs {
-  noise_amd::CsTableView t{};
-  noise_amd::CsWindowView w{};  // replay windows: allocated by the first windowed call
-  void *scratch = nullptr;  // grow-only; the sort's tables and the private index / nonce copies
-  size_t scratch_size = 0;
-};
-
-namespace {
-
-constexpr uint64_t kCsMaxSess = 0xfffffffeull;  // 2^32-2: 0xffffffff marks a refused record
-constexpr uint64_t kCsMaxRec = 1ull << 31;
-constexpr uint64_t kCsWinRow = NOISE_GPU_CS_WINDOW / 8;  // bytes of a session's bitmap
-
-// the table's scratch, >= bytes; the smaller one is wiped and freed
-// stream-ordered after the launches that still use it
-hipError_t cs_scratch(noise_gpu_cs *cs, size_t bytes, hipStream_t st) {
-  if (bytes <= cs->scratch_size) return hipSuccess;
-  hipError_t e = noise_amd::dev_wipe_free(cs->scratch, cs->scratch_size, st);
-  cs->scratch = nullptr;
-  cs->scratch_size = 0;
-  if (e != hipSuccess) return e;
-  if ((e = noise_amd::dev_alloc(&cs->scratch, bytes, st)) != hipSuccess) return e;
-  cs->scratch_size = bytes;
-  return hipSuccess;
-}
-
-int cs_check_range(const noise_gpu_cs *cs, uint64_t first, uint64_t count) {
-  if (first + count < first) return arg_fail("first + count overflows");
-  if (!cs) return arg_fail("null table");
-  if (first + count > cs->t.nsess) return arg_fail("sessions [first, first + count) outside the table");
-  return NOISE_GPU_OK;
-}
-
-int cs_check_assign(const noise_gpu_cs *cs, const void *d_sess, uint64_t sess_stride,
-                    const void *d_nonce, uint64_t nonce_stride, uint64_t nrec) {
-  if (sess_stride == 0 || (sess_stride & 3u)) return arg_fail("session stride must be a non-zero multiple of 4");
-  if (nonce_stride == 0 || (nonce_stride & 7u)) return arg_fail("nonce stride must be a non-zero multiple of 8");
-  if (nrec > kCsMaxRec) return arg_fail("more than 2^31 records in one batch");
-  if (!cs) return arg_fail("null table");
-  if (nrec == 0) return NOISE_GPU_OK;
-  if (!d_sess || !d_nonce) return arg_fail("null session / nonce array");
-  if ((reinterpret_cast<uintptr_t>(d_sess) & 3u) || (reinterpret_cast<uintptr_t>(d_nonce) & 7u))
-    return arg_fail("session / nonce arrays must be 4 / 8-byte aligned");
-  return NOISE_GPU_OK;
-}
-
-int cs_records(bool decrypt, noise_gpu_cs *cs, noise_gpu_record *d_recs, uint64_t nrec,
-               const uint8_t *d_in, uint8_t *d_out, const uint8_t *d_ad, uint8_t *d_status,
-               uint64_t len_sum, void *stream) {
-  if (nrec > kCsMaxRec) return arg_fail("more than 2^31 records in one batch");
-  if (!cs) return arg_fail("null table");
-  if (nrec == 0) return NOISE_GPU_OK;
-  if (!d_recs || !d_in || !d_out || (decrypt && !d_status))
-    return arg_fail(decrypt ? "null descriptors / buffers / status" : "null descriptors / buffers");
-  if (reinterpret_cast<uintptr_t>(d_recs) & 7u) return arg_fail("descriptors must be 8-byte aligned");
-  int rc = check_device();
-  if (rc) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  // scratch: the sort's tables | a private copy of the descriptors, in which
-  // a refused record's key_idx is out of range for the AEAD kernels
-  const size_t sort_bytes = align16(noise_amd::cs_assign_scratch_bytes(nrec));
-  HIP_TRY(cs_scratch(cs, sort_bytes + nrec * sizeof(noise_gpu_record), st));
-  uint8_t *base = static_cast<uint8_t *>(cs->scratch);
-  noise_gpu_record *priv = reinterpret_cast<noise_gpu_record *>(base + sort_bytes);
-  HIP_TRY(hipMemcpyAsync(priv, d_recs, nrec * sizeof(noise_gpu_record), hipMemcpyDeviceToDevice, st));
-  constexpr uint64_t kRec = sizeof(noise_gpu_record);
-  uint8_t *caller = reinterpret_cast<uint8_t *>(d_recs), *mine = reinterpret_cast<uint8_t *>(priv);
-  const noise_amd::CsAssign a{caller + offsetof(noise_gpu_record, key_idx), kRec,
-                              caller + offsetof(noise_gpu_record, nonce), kRec,
-                              mine + offsetof(noise_gpu_record, nonce), kRec,
-                              mine + offsetof(noise_gpu_record, key_idx), kRec,
-                              decrypt ? nullptr : d_status, nrec};
-  HIP_TRY(noise_amd::launch_cs_assign(cs->t, a, base, st));
-  HIP_TRY(noise_amd::launch_aead_records(decrypt, cs->t.keys, cs->t.nsess, priv, nrec, d_in, d_out,
-                                         d_ad, decrypt ? d_status : nullptr, st, len_sum));
-  if (decrypt)
-    HIP_TRY(noise_amd::launch_cs_fix(a.sess, kRec, a.kill, kRec, d_status, nrec, st));
-  return NOISE_GPU_OK;
-}
-
-int cs_sessions(bool decrypt, noise_gpu_cs *cs, const uint32_t *d_sess, const uint8_t *d_in,
-                uint64_t in_stride, uint8_t *d_out, uint64_t out_stride, uint32_t len,
-                uint8_t *d_status, uint64_t nrec, void *stream) {
-  if (nrec > kCsMaxRec) return arg_fail("more than 2^31 records in one batch");
-  if (!cs) return arg_fail("null table");
-  if (nrec == 0) return NOISE_GPU_OK;
-  if (!d_sess || (reinterpret_cast<uintptr_t>(d_sess) & 3u))
-    return arg_fail("null or unaligned session array");
-  int rc = check_uniform(decrypt, d_in, in_stride, d_out, out_stride, len, nullptr, 0, d_status, nrec);
-  if (rc) return rc;
-  if (!noise_amd::sessions_supported(len, d_in, in_stride, d_out, out_stride))
-    return arg_fail("sessions batches need a tile length and 16-byte aligned buffers/strides "
-                    "(see noise_gpu_encrypt_sessions)");
-  if ((rc = check_device())) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  // scratch: the sort's tables | the nonces | a private copy of the index, in
-  // which a refused record carries an out-of-range value
-  const size_t sort_bytes = align16(noise_amd::cs_assign_scratch_bytes(nrec));
-  HIP_TRY(cs_scratch(cs, sort_bytes + 12 * nrec, st));
-  uint8_t *base = static_cast<uint8_t *>(cs->scratch);
-  uint8_t *nonces = base + sort_bytes, *idx = nonces + 8 * nrec;
-  HIP_TRY(hipMemcpyAsync(idx, d_sess, 4 * nrec, hipMemcpyDeviceToDevice, st));
-  const uint8_t *sess = reinterpret_cast<const uint8_t *>(d_sess);
-  const noise_amd::CsAssign a{sess, 4, nonces, 8, nullptr, 0, idx, 4, decrypt ? nullptr : d_status, nrec};
-  HIP_TRY(noise_amd::launch_cs_assign(cs->t, a, base, st));
-  HIP_TRY(noise_amd::launch_aead_sessions(decrypt, cs->t.keys, cs->t.nsess,
-                                          reinterpret_cast<const uint32_t *>(idx),
-                                          reinterpret_cast<const uint64_t *>(nonces), d_in, in_stride,
-                                          d_out, out_stride, len, decrypt ? d_status : nullptr, nrec, st));
-  if (decrypt) HIP_TRY(noise_amd::launch_cs_fix(sess, 4, idx, 4, d_status, nrec, st));
-  return NOISE_GPU_OK;
-}
-
-// ---- replay windows ----
-hipError_t cs_window_clear(noise_gpu_cs *cs, uint64_t first, uint64_t count, hipStream_t st) {
-  if (count == 0) return hipSuccess;
-  hipError_t e = hipMemsetAsync(cs->w.next + first, 0, 8 * count, st);
-  if (e != hipSuccess) return e;
-  return hipMemsetAsync(reinterpret_cast<uint8_t *>(cs->w.bits) + kCsWinRow * first, 0,
-                        kCsWinRow * count, st);
-}
-
-// the window rows, fresh on the first call
-hipError_t cs_window_rows(noise_gpu_cs *cs, hipStream_t st) {
-  if (cs->w.next) return hipSuccess;
-  const uint64_t n = cs->t.nsess;
-  void *next = nullptr, *bits = nullptr;
-  hipError_t e = noise_amd::dev_alloc(&next, 8 * n, st);
-  if (e != hipSuccess) return e;
-  if ((e = noise_amd::dev_alloc(&bits, kCsWinRow * n, st)) != hipSuccess) {
-    (void)noise_amd::dev_wipe_free(next, 0, st);
-    return e;
-  }
-  cs->w.next = static_cast<uint64_t *>(next);
-  cs->w.bits = static_cast<uint32_t *>(bits);
-  return cs_window_clear(cs, 0, n, st);
-}
-
-// the three phases of a windowed decrypt around the AEAD launch `aead`, which
-// works on the private index at `kill`; scratch: commit | pre-status | priv
-template <class Aead>
-int cs_window_decrypt(noise_gpu_cs *cs, const noise_amd::CwBatch &b, size_t commit_bytes,
-                      uint8_t *kill, uint64_t kill_stride, const noise_gpu_record *recs,
-                      uint8_t *d_out, uint64_t out_stride, uint32_t len, uint8_t *d_status,
-                      hipStream_t st, Aead aead) {
-  uint8_t *base = static_cast<uint8_t *>(cs->scratch);
-  uint8_t *pre = base + commit_bytes;
-  HIP_TRY(noise_amd::launch_cw_filter(cs->t, cs->w, b, pre, kill, kill_stride, st));
-  HIP_TRY(aead());
-  HIP_TRY(noise_amd::launch_cw_commit(cs->t, cs->w, b, d_status, base, st));
-  HIP_TRY(noise_amd::launch_cw_finish(pre, d_status, recs, d_out, out_stride, len, b.nrec, st));
-  return NOISE_GPU_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int noise_gpu_cs_create(uint64_t nsess, noise_gpu_cs **out) {
-  if (!out) return arg_fail("null output");
-  *out = nullptr;
-  if (nsess == 0 || nsess > kCsMaxSess) return arg_fail("a CipherState table holds 1 .. 2^32-2 sessions");
-  int rc = check_device();
-  if (rc) return rc;
-  noise_gpu_cs *cs = new (std::nothrow) noise_gpu_cs();
-  if (!cs) return arg_fail("out of host memory");
-  cs->t.nsess = (uint32_t)nsess;
-  hipError_t e = hipMalloc(&cs->t.keys, nsess * 32);
-  if (e == hipSuccess) e = hipMalloc(&cs->t.ctr, nsess * 8);
-  if (e == hipSuccess) e = hipMalloc(&cs->t.start, nsess * 4);
-  if (e == hipSuccess) e = hipMemset(cs->t.keys, 0, nsess * 32);
-  if (e == hipSuccess) e = hipMemset(cs->t.ctr, 0, nsess * 8);
-  if (e == hipSuccess) e = hipMemset(cs->t.start, 0, nsess * 4);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    if (cs->t.keys) (void)hipFree(cs->t.keys);
-    if (cs->t.ctr) (void)hipFree(cs->t.ctr);
-    if (cs->t.start) (void)hipFree(cs->t.start);
-    delete cs;
-    return hip_fail(e, "CipherState table allocation");
-  }
-  *out = cs;
-  return NOISE_GPU_OK;
-}
-
-int noise_gpu_cs_destroy(noise_gpu_cs *cs) {
-  if (!cs) return NOISE_GPU_OK;
-  int rc = NOISE_GPU_OK;
-  auto keep = [&rc](hipError_t e) {
-    if (e != hipSuccess) rc = hip_fail(e, "noise_gpu_cs_destroy");
-  };
-  keep(hipDeviceSynchronize());  // the table's last calls, whatever stream they ran on
-  const uint64_t n = cs->t.nsess;
-  keep(hipMemset(cs->t.keys, 0, n * 32));
-  keep(hipMemset(cs->t.ctr, 0, n * 8));
-  keep(hipMemset(cs->t.start, 0, n * 4));
-  keep(noise_amd::dev_wipe_free(cs->w.next, n * 8, nullptr));
-  keep(noise_amd::dev_wipe_free(cs->w.bits, n * kCsWinRow, nullptr));
-  keep(noise_amd::dev_wipe_free(cs->scratch, cs->scratch_size, nullptr));
-  keep(hipDeviceSynchronize());
-  (void)hipFree(cs->t.keys);
-  (void)hipFree(cs->t.ctr);
-  (void)hipFree(cs->t.start);
-  delete cs;
-  return rc;
-}
-
-int noise_gpu_cs_set(noise_gpu_cs *cs, uint64_t first, uint64_t count, const uint8_t *d_keys,
-                     uint64_t key_stride, const uint64_t *d_n, void *stream) {
-  if (d_keys && key_stride < 32) return arg_fail("key rows are 32 bytes: key_stride >= 32");
-  if (reinterpret_cast<uintptr_t>(d_n) & 7u) return arg_fail("counters must be 8-byte aligned");
-  int rc = cs_check_range(cs, first, count);
-  if (rc || count == 0) return rc;
-  if (!d_keys && !d_n) return arg_fail("neither key rows nor counters given");
-  if ((rc = check_device())) return rc;
-  HIP_TRY(noise_amd::launch_cs_set(cs->t, first, count, d_keys, key_stride, d_n, (hipStream_t)stream));
-  // a new key starts a new nonce space
-  if (d_keys && cs->w.next) HIP_TRY(cs_window_clear(cs, first, count, (hipStream_t)stream));
-  return NOISE_GPU_OK;
-}
-
-int noise_gpu_cs_get(const noise_gpu_cs *cs, uint64_t first, uint64_t count, uint8_t *d_keys,
-                     uint64_t *d_n, void *stream) {
-  int rc = cs_check_range(cs, first, count);
-  if (rc || count == 0) return rc;
-  if ((rc = check_device())) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  if (d_keys)
-    HIP_TRY(hipMemcpyAsync(d_keys, cs->t.keys + 32 * first, 32 * count, hipMemcpyDeviceToDevice, st));
-  if (d_n) HIP_TRY(hipMemcpyAsync(d_n, cs->t.ctr + first, 8 * count, hipMemcpyDeviceToDevice, st));
-  return NOISE_GPU_OK;
-}
-
-int noise_gpu_cs_rekey(noise_gpu_cs *cs, const uint32_t *d_sess, uint64_t count, void *stream) {
-  if (reinterpret_cast<uintptr_t>(d_sess) & 3u) return arg_fail("session array must be 4-byte aligned");
-  if (!cs) return arg_fail("null table");
-  if (!d_sess) count = cs->t.nsess;
-  if (count == 0) return NOISE_GPU_OK;
-  int rc = check_device();
-  if (rc) return rc;
-  HIP_TRY(noise_amd::launch_cs_rekey(cs->t, d_sess, count, (hipStream_t)stream));
-  return NOISE_GPU_OK;
-}
-
-int noise_gpu_cs_assign(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t sess_stride,
-                        uint8_t *d_nonce, uint64_t nonce_stride, uint8_t *d_status, uint64_t nrec,
-                        void *stream) {
-  int rc = cs_check_assign(cs, d_sess, sess_stride, d_nonce, nonce_stride, nrec);
-  if (rc || nrec == 0) return rc;
-  if ((rc = check_device())) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(cs_scratch(cs, noise_amd::cs_assign_scratch_bytes(nrec), st));
-  const noise_amd::CsAssign a{d_sess, sess_stride, d_nonce, nonce_stride, nullptr, 0,
-                              nullptr, 0, d_status, nrec};
-  HIP_TRY(noise_amd::launch_cs_assign(cs->t, a, cs->scratch, st));
-  return NOISE_GPU_OK;
-}
-
-int noise_gpu_cs_encrypt_records(noise_gpu_cs *cs, noise_gpu_record *d_recs, uint64_t nrec,
-                                 const uint8_t *d_in, uint8_t *d_out, const uint8_t *d_ad,
-                                 uint8_t *d_status, uint64_t len_sum, void *stream) {
-  return cs_records(false, cs, d_recs, nrec, d_in, d_out, d_ad, d_status, len_sum, stream);
-}
-
-int noise_gpu_cs_decrypt_records(noise_gpu_cs *cs, noise_gpu_record *d_recs, uint64_t nrec,
-                                 const uint8_t *d_in, uint8_t *d_out, const uint8_t *d_ad,
-                                 uint8_t *d_status, uint64_t len_sum, void *stream) {
-  return cs_records(true, cs, d_recs, nrec, d_in, d_out, d_ad, d_status, len_sum, stream);
-}
-
-int noise_gpu_cs_encrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess, const uint8_t *d_in,
-                                  uint64_t in_stride, uint8_t *d_out, uint64_t out_stride,
-                                  uint32_t len, uint8_t *d_status, uint64_t nrec, void *stream) {
-  return cs_sessions(false, cs, d_sess, d_in, in_stride, d_out, out_stride, len, d_status, nrec, stream);
-}
-
-int noise_gpu_cs_decrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess, const uint8_t *d_in,
-                                  uint64_t in_stride, uint8_t *d_out, uint64_t out_stride,
-                                  uint32_t len, uint8_t *d_status, uint64_t nrec, void *stream) {
-  return cs_sessions(true, cs, d_sess, d_in, in_stride, d_out, out_stride, len, d_status, nrec, stream);
-}
-
-int noise_gpu_cswin_reset(noise_gpu_cs *cs, uint64_t first, uint64_t count, void *stream) {
-  int rc = cs_check_range(cs, first, count);
-  if (rc || count == 0) return rc;
-  if ((rc = check_device())) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  const bool fresh = !cs->w.next;
-  HIP_TRY(cs_window_rows(cs, st));
-  if (!fresh) HIP_TRY(cs_window_clear(cs, first, count, st));
-  return NOISE_GPU_OK;
-}
-
-int noise_gpu_cswin_get(const noise_gpu_cs *cs, uint64_t first, uint64_t count, uint64_t *d_next,
-                        uint8_t *d_bits, void *stream) {
-  if (reinterpret_cast<uintptr_t>(d_next) & 7u) return arg_fail("next array must be 8-byte aligned");
-  int rc = cs_check_range(cs, first, count);
-  if (rc || count == 0) return rc;
-  if ((rc = check_device())) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  if (!cs->w.next) {  // never used a window: the fresh state
-    if (d_next) HIP_TRY(hipMemsetAsync(d_next, 0, 8 * count, st));
-    if (d_bits) HIP_TRY(hipMemsetAsync(d_bits, 0, kCsWinRow * count, st));
-    return NOISE_GPU_OK;
-  }
-  if (d_next)
-    HIP_TRY(hipMemcpyAsync(d_next, cs->w.next + first, 8 * count, hipMemcpyDeviceToDevice, st));
-  if (d_bits)
-    HIP_TRY(hipMemcpyAsync(d_bits, reinterpret_cast<const uint8_t *>(cs->w.bits) + kCsWinRow * first,
-                           kCsWinRow * count, hipMemcpyDeviceToDevice, st));
-  return NOISE_GPU_OK;
-}
-
-int noise_gpu_cswin_filter(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t sess_stride,
-                           const uint8_t *d_nonce, uint64_t nonce_stride, uint8_t *d_status,
-                           uint64_t nrec, void *stream) {
-  int rc = cs_check_assign(cs, d_sess, sess_stride, d_nonce, nonce_stride, nrec);
-  if (rc || nrec == 0) return rc;
-  if (!d_status) return arg_fail("null status buffer");
-  if ((rc = check_device())) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(cs_window_rows(cs, st));
-  const noise_amd::CwBatch b{d_sess, sess_stride, d_nonce, nonce_stride, nrec};
-  HIP_TRY(noise_amd::launch_cw_filter(cs->t, cs->w, b, d_status, nullptr, 0, st));
-  return NOISE_GPU_OK;
-}
-
-int noise_gpu_cswin_commit(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t sess_stride,
-                           const uint8_t *d_nonce, uint64_t nonce_stride, uint8_t *d_status,
-                           uint64_t nrec, void *stream) {
-  int rc = cs_check_assign(cs, d_sess, sess_stride, d_nonce, nonce_stride, nrec);
-  if (rc || nrec == 0) return rc;
-  if (!d_status) return arg_fail("null status buffer");
-  if ((rc = check_device())) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(cs_window_rows(cs, st));
-  HIP_TRY(cs_scratch(cs, noise_amd::cw_commit_scratch_bytes(nrec), st));
-  const noise_amd::CwBatch b{d_sess, sess_stride, d_nonce, nonce_stride, nrec};
-  HIP_TRY(noise_amd::launch_cw_commit(cs->t, cs->w, b, d_status, cs->scratch, st));
-  return NOISE_GPU_OK;
-}
-
-int noise_gpu_cswin_decrypt_records(noise_gpu_cs *cs, const noise_gpu_record *d_recs, uint64_t nrec,
-                                    const uint8_t *d_in, uint8_t *d_out, const uint8_t *d_ad,
-                                    uint8_t *d_status, uint64_t len_sum, void *stream) {
-  if (nrec > kCsMaxRec) return arg_fail("more than 2^31 records in one batch");
-  if (!cs) return arg_fail("null table");
-  if (nrec == 0) return NOISE_GPU_OK;
-  if (!d_recs || !d_in || !d_out || !d_status) return arg_fail("null descriptors / buffers / status");
-  if (reinterpret_cast<uintptr_t>(d_recs) & 7u) return arg_fail("descriptors must be 8-byte aligned");
-  int rc = check_device();
-  if (rc) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(cs_window_rows(cs, st));
-  // scratch: the commit's | the prefilter's verdicts | a private copy of the
-  // descriptors, in which a refused record's key_idx is out of range
-  const size_t commit_bytes = align16(noise_amd::cw_commit_scratch_bytes(nrec));
-  const size_t pre_bytes = align16(nrec);
-  HIP_TRY(cs_scratch(cs, commit_bytes + pre_bytes + nrec * sizeof(noise_gpu_record), st));
-  uint8_t *base = static_cast<uint8_t *>(cs->scratch);
-  noise_gpu_record *priv = reinterpret_cast<noise_gpu_record *>(base + commit_bytes + pre_bytes);
-  HIP_TRY(hipMemcpyAsync(priv, d_recs, nrec * sizeof(noise_gpu_record), hipMemcpyDeviceToDevice, st));
-  constexpr uint64_t kRec = sizeof(noise_gpu_record);
-  const uint8_t *caller = reinterpret_cast<const uint8_t *>(d_recs);
-  const noise_amd::CwBatch b{caller + offsetof(noise_gpu_record, key_idx), kRec,
-                             caller + offsetof(noise_gpu_record, nonce), kRec, nrec};
-  return cs_window_decrypt(
-      cs, b, commit_bytes, reinterpret_cast<uint8_t *>(priv) + offsetof(noise_gpu_record, key_idx), kRec,
-      d_recs, d_out, 0, 0, d_status, st, [&] {
-        return noise_amd::launch_aead_records(true, cs->t.keys, cs->t.nsess, priv, nrec, d_in, d_out,
-                                              d_ad, d_status, st, len_sum);
-      });
-}
-
-int noise_gpu_cswin_decrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess,
-                                     const uint64_t *d_nonces, const uint8_t *d_in,
-                                     uint64_t in_stride, uint8_t *d_out, uint64_t out_stride,
-                                     uint32_t len, uint8_t *d_status, uint64_t nrec, void *stream) {
-  if (nrec > kCsMaxRec) return arg_fail("more than 2^31 records in one batch");
-  if (!cs) return arg_fail("null table");
-  if (nrec == 0) return NOISE_GPU_OK;
-  if (!d_sess || (reinterpret_cast<uintptr_t>(d_sess) & 3u))
-    return arg_fail("null or unaligned session array");
-  if (!d_nonces || (reinterpret_cast<uintptr_t>(d_nonces) & 7u))
-    return arg_fail("null or unaligned nonce array");
-  int rc = check_uniform(true, d_in, in_stride, d_out, out_stride, len, nullptr, 0, d_status, nrec);
-  if (rc) return rc;
-  if (!noise_amd::sessions_supported(len, d_in, in_stride, d_out, out_stride))
-    return arg_fail("sessions batches need a tile length and 16-byte aligned buffers/strides "
-                    "(see noise_gpu_encrypt_sessions)");
-  if ((rc = check_device())) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(cs_window_rows(cs, st));
-  // scratch: the commit's | the prefilter's verdicts | a private copy of the
-  // index, in which a refused record carries an out-of-range value
-  const size_t commit_bytes = align16(noise_amd::cw_commit_scratch_bytes(nrec));
-  const size_t pre_bytes = align16(nrec);
-  HIP_TRY(cs_scratch(cs, commit_bytes + pre_bytes + 4 * nrec, st));
-  uint8_t *idx = static_cast<uint8_t *>(cs->scratch) + commit_bytes + pre_bytes;
-  HIP_TRY(hipMemcpyAsync(idx, d_sess, 4 * nrec, hipMemcpyDeviceToDevice, st));
-  const noise_amd::CwBatch b{reinterpret_cast<const uint8_t *>(d_sess), 4,
-                             reinterpret_cast<const uint8_t *>(d_nonces), 8, nrec};
-  return cs_window_decrypt(cs, b, commit_bytes, idx, 4, nullptr, d_out, out_stride, len, d_status, st, [&] {
-    return noise_amd::launch_aead_sessions(true, cs->t.keys, cs->t.nsess,
-                                           reinterpret_cast<const uint32_t *>(idx), d_nonces, d_in,
-                                           in_stride, d_out, out_stride, len, d_status, nrec, st);
-  });
 }
 
 int noise_gpu_x25519(const uint8_t *d_scalars, const uint8_t *d_points,

@@ -34,6 +34,7 @@
 // Scratch and the companion streams are cached per (device, stream)
 // (stream_res.hpp).
 #include "chachapoly_device.hpp"
+#include "cstate_device.hpp"  // key_row_zero, wave_incl_scan
 #include "launchers.hpp"
 #include "mtile_kernel.hpp"
 #include "tile_kernel.hpp"
@@ -97,14 +98,6 @@ constexpr uint64_t kClassifyAvgLen = 2048;  // below kClassifyMin: classify when
 constexpr uint64_t kSegCapMax = NOISE_SEG_CAP;  // 16 Mi segments = 16 GiB per call
 // (the grid cap of the per-class launches, NOISE_GRID_CAP: tile_launch.hpp)
 
-// an all-zero key row is "no key" (Noise HasKey() false, e.g. the rows
-// noise_gpu_hs_split leaves for failed handshakes): never used to encrypt
-__device__ __forceinline__ bool key_row_zero(const uint8_t *keys, uint32_t ki) {
-  const uint4 *kp = reinterpret_cast<const uint4 *>(keys + 32ull * ki);
-  const uint4 a = kp[0], b = kp[1];
-  return (a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w) == 0u;
-}
-
 // records the tile / segment kernels cannot take go to the generic class,
 // which also reports bad key rows (index out of range or all zero); the
 // others by their length (len_class, tile_classes.hpp)
@@ -139,16 +132,6 @@ static_assert(sizeof(RecHdr) == 8 * kHdrWords, "scratch header layout");
 __device__ __forceinline__ int fin_bucket(uint32_t nf) {
   const int b = 31 - __builtin_clz(nf | 1u);
   return b < kFinBuckets - 1 ? b : kFinBuckets - 1;
-}
-
-// wave-wide inclusive prefix sum (all 64 lanes participate)
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t t = (uint32_t)__shfl((int)v, (int)(lane >= (uint32_t)d ? lane - d : lane));
-    if (lane >= (uint32_t)d) v += t;
-  }
-  return v;
 }
 
 __device__ __forceinline__ unsigned long long wave_incl_scan64(unsigned long long v,

@@ -2,9 +2,12 @@
 csrc/cswin_kernels.hip and the sort it shares with nonce assignment
 (csrc/cstate_kernels.hip) compiled as host C++ against the HIP stand-in in
 tools/emu and run as a stand-alone program (tools/emu/emu_cswin.cpp) under
-AddressSanitizer.  The build caps the grid at 3 workgroups and cuts the sort
-into 640-record chunks; tables, window rows, batches, outputs and scratch are
-allocated at their exact sizes, so an index past any of them is an ASan report.
+AddressSanitizer.  Every batch goes through cs_window_call
+(csrc/cstate_calls.hpp), the composition the C ABI runs: scratch carve, private
+copy, prefilter, commit, finish.  The build caps the grid at 3 workgroups and
+cuts the sort into 640-record chunks; tables, window rows, batches and outputs
+are allocated at their exact sizes and the scratch at cs_scratch_layout's
+total, so an index past any of them or past a scratch region is an ASan report.
 Every case runs two batches in sequence on windows that have seen traffic
 (bases at 0, across 2^32, and running into the 2^64-2 limit) and is checked
 inside the program against the plain loop of include/noise_gpu.h over
@@ -12,8 +15,9 @@ noise::ReplayWindow: pre-statuses and refused marks of the prefilter (which
 must not write to the table), final statuses, next and bitmap rows, and every
 output byte (accepted: kept; post-authentication replay: zeroed; everything
 else and every gap: untouched).  A case fails if the model never produced a
-status it is about.  The AEAD between prefilter and commit is a stand-in
-there.  Test infrastructure only: the product runs these kernels on the GPU
+status it is about.  Only the AEAD launch between prefilter and commit is a
+stand-in there; it is also where the prefilter's results are checked.  Test
+infrastructure only: the product runs these kernels on the GPU
 (tests/test_gpu_cswin.py)."""
 import os
 import subprocess

@@ -519,6 +519,53 @@ def test_end_to_end_records_classified(split_keys, oracle, in_place):
     end_to_end(split_keys, oracle, 80 + in_place, "desc", in_place, 2100, [1, 16, 64, 100, 192, 255, 256])
 
 
+def test_one_table_across_call_kinds(oracle):
+    """One table (257 sessions: two radix passes) whose grow-only scratch is laid
+    out four ways in turn (cs_scratch_layout, csrc/cstate_calls.hpp): in-order
+    arrays, windowed descriptors (which grows it), a bare assign, windowed
+    arrays.  Each call against the oracle and the host models."""
+    n = 257
+    rng = np.random.default_rng(n)
+    t, keys = make_table(n, rng)
+    tx = noise_amd.CipherStateTable(n)  # the peer that wrote what the windowed calls receive
+    tx.set(0, n, _dev(keys.reshape(-1)), 32, _dev(np.full(n, 7, np.uint64)))
+    ctr, wins = np.full(n, 7, np.uint64), {}
+    # 1. noise_gpu_cs_encrypt_sessions, 65 records of 64 B
+    L, nrec = 64, 65
+    sess = rng.integers(0, n, nrec).astype(np.uint32)
+    pt = rng.integers(0, 256, (nrec, L), dtype=np.uint8)
+    ct = torch.full((nrec * (L + 16),), 0xA5, dtype=torch.uint8, device="cuda")
+    st = torch.full((nrec,), 0x77, dtype=torch.uint8, device="cuda")
+    t.encrypt_sessions(_dev(sess), _dev(pt.reshape(-1)), L, ct, L + 16, L, nrec, d_status=st)
+    torch.cuda.synchronize()
+    assert not _host(st).any()
+    got = _host(ct).reshape(nrec, L + 16)
+    for i, s in enumerate(sess):
+        assert got[i].tobytes() == oracle.encrypt(keys[s].tobytes(), int(ctr[s]), b"", pt[i].tobytes()), i
+        ctr[s] += 1
+    # 2. noise_gpu_cswin_decrypt_records, 1500 records of mixed lengths
+    sent = send(tx, rng, n, 1500, rng.choice([1, 64, 100, 1024, 3000], 1500))
+    receive(t, keys, wins, scramble(rng, sent, [], n, 1500), oracle, "desc", False, ALL - {"entry"})
+    # 3. noise_gpu_cs_assign, 1 record
+    s = int(sess[0])
+    d_n = torch.zeros(1, dtype=torch.int64, device="cuda")
+    st = torch.full((1,), 0x77, dtype=torch.uint8, device="cuda")
+    t.assign(_dev(np.array([s], np.uint32)), d_n, 1, st)
+    torch.cuda.synchronize()
+    assert int(_host(d_n, np.uint64)[0]) == int(ctr[s]) and int(_host(st)[0]) == OK
+    ctr[s] += 1
+    # 4. noise_gpu_cswin_decrypt_sessions, 65 records: new ones of 20 sessions and late copies from step 2
+    sent4 = send(tx, rng, 20, 50, np.full(50, L))
+    late = [r for r in sent if len(r[3]) == L]
+    receive(t, keys, wins, scramble(rng, sent4, late, n, 65), oracle, "sessions", False, ALL)
+    d = torch.zeros(n, dtype=torch.int64, device="cuda")
+    t.get(0, n, d_n=d)
+    torch.cuda.synchronize()
+    assert np.array_equal(_host(d, np.uint64), ctr)  # the windowed calls never moved the in-order counters
+    tx.close()
+    t.close()
+
+
 # ---- the C++ view ------------------------------------------------------------------
 def test_cpp_device_windows():
     """noise::DeviceCipherStates' windowed calls against noise::ReplayWindow, and

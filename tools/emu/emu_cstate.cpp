@@ -1,21 +1,27 @@
 // emu_cstate.cpp -- the CipherState-table kernels (cstate_kernels.hip,
 // unmodified) on the CPU under AddressSanitizer: nonce assignment, set and
 // rekey, checked against a plain loop (a map of counters and the rule of
-// include/noise_gpu.h) and the oracle's rekey.  The build caps the grid at 3
-// workgroups and cuts the sort into 640-record chunks (a full batch of 8
-// steps and a partial one), so at 5000 records every workgroup loops over
-// several chunks.  Every buffer is allocated at its exact size:
-// an index past a table, a batch or the scratch is an ASan report.
+// include/noise_gpu.h) and the oracle's rekey.  A batch goes through the
+// in-order call of cstate_calls.hpp itself -- the scratch carve, the private
+// copy, the assignment and, in the decrypt direction, k_cs_fix -- as the C ABI
+// runs it; only the AEAD launch in the middle is a stand-in (a verdict per
+// record, from the private index the kernels would read).  The build caps the
+// grid at 3 workgroups and cuts the sort into 640-record chunks (a full batch
+// of 8 steps and a partial one), so at 5000 records every workgroup loops over
+// several chunks.  Every buffer is allocated at its exact size, the scratch at
+// cs_scratch_layout's total: an index past a table, a batch or a scratch
+// region is an ASan report.
 //   emu_cstate            all cases
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <map>
 #include <random>
 #include <vector>
 
-#include "launchers.hpp"
+#include "cstate_calls.hpp"
 
 extern "C" void oracle_rekey(const uint8_t key[32], uint8_t new_key[32]);
 
@@ -51,8 +57,8 @@ struct Table {
   }
 };
 
-// one batch through launch_cs_assign, both addressing forms, against the loop
-void run_batch(const char *name, Table &t, const std::vector<uint32_t> &sess, bool desc) {
+// one batch through cs_inorder_call, both addressing forms, against the loop
+void run_batch(const char *name, Table &t, const std::vector<uint32_t> &sess, bool desc, bool decrypt = false) {
   const uint64_t nrec = sess.size();
   // expected: the plain loop
   std::map<uint32_t, uint64_t> n;
@@ -73,13 +79,13 @@ void run_batch(const char *name, Table &t, const std::vector<uint32_t> &sess, bo
   }
   std::vector<uint64_t> want_ctr = t.ctr;
   for (auto &kv : n) want_ctr[kv.first] = kv.second;
+  CHECK(!decrypt || std::count(want_st.begin(), want_st.end(), NOISE_GPU_REC_NONCE),
+        "the loop refused no record: nothing for k_cs_fix to restore");
 
-  // the batch, exactly sized
+  // the batch and the call's scratch, exactly sized
   std::vector<noise_gpu_record> recs(desc ? nrec : 0);
   std::vector<uint32_t> idx(desc ? 0 : nrec);
-  std::vector<uint64_t> nonce(desc ? 0 : nrec, 0x5a5a5a5a5a5a5a5aull);
   std::vector<uint8_t> status(nrec, 0xA5);
-  std::vector<uint32_t> kill(nrec);
   for (uint64_t i = 0; i < nrec; ++i) {
     if (desc) {
       std::memset(&recs[i], 0x77, sizeof(noise_gpu_record));
@@ -88,44 +94,47 @@ void run_batch(const char *name, Table &t, const std::vector<uint32_t> &sess, bo
     } else {
       idx[i] = sess[i];
     }
-    kill[i] = sess[i];
   }
-  CsAssign a{};
-  if (desc) {
-    a.sess = reinterpret_cast<uint8_t *>(recs.data()) + offsetof(noise_gpu_record, key_idx);
-    a.nonce = reinterpret_cast<uint8_t *>(recs.data()) + offsetof(noise_gpu_record, nonce);
-    a.sess_stride = a.nonce_stride = sizeof(noise_gpu_record);
-  } else {
-    a.sess = reinterpret_cast<uint8_t *>(idx.data());
-    a.sess_stride = 4;
-    a.nonce = reinterpret_cast<uint8_t *>(nonce.data());
-    a.nonce_stride = 8;
-  }
-  a.kill = reinterpret_cast<uint8_t *>(kill.data());
-  a.kill_stride = 4;
-  a.status = status.data();
-  a.nrec = nrec;
-  std::vector<uint8_t> scratch(cs_assign_scratch_bytes(nrec));
-  const hipError_t e = launch_cs_assign(t.view(), a, scratch.data(), nullptr);
+  std::vector<uint8_t> scratch(cs_scratch_layout(false, desc, nrec).total, 0x5a);
+  // the stand-in AEAD keeps where the kernels would read the private index and
+  // the nonces; decrypt: its verdict is BAD_KEY where they would find no key row
+  CsColumns mine{};
+  const hipError_t e = cs_inorder_call(
+      decrypt, t.view(), desc ? cs_columns(recs.data()) : cs_columns(idx.data(), nullptr), nrec, scratch.data(),
+      status.data(), nullptr, [&](const CsColumns &priv) {
+        mine = priv;
+        for (uint64_t i = 0; decrypt && i < nrec; ++i) {
+          uint32_t s;
+          std::memcpy(&s, mine.sess + i * mine.sess_stride, 4);
+          status[i] = s >= t.nsess || t.keyless(s) ? NOISE_GPU_REC_BAD_KEY : NOISE_GPU_REC_OK;
+        }
+        return hipSuccess;
+      });
   CHECK(e == hipSuccess, "launch error %d", (int)e);
   for (uint64_t i = 0; i < nrec; ++i) {
     CHECK(status[i] == want_st[i], "record %llu (session %u): status %u, want %u",
           (unsigned long long)i, sess[i], status[i], want_st[i]);
-    const uint64_t got = desc ? recs[i].nonce : nonce[i];
+    uint64_t got;  // what the AEAD kernels are given
+    uint32_t kill;
+    std::memcpy(&got, mine.nonce + i * mine.nonce_stride, 8);
+    std::memcpy(&kill, mine.sess + i * mine.sess_stride, 4);
     if (want_st[i] == NOISE_GPU_REC_OK)
-      CHECK(got == want_nonce[i], "record %llu (session %u): nonce %llu, want %llu",
-            (unsigned long long)i, sess[i], (unsigned long long)got,
+      CHECK(got == want_nonce[i] && (!desc || recs[i].nonce == got),
+            "record %llu (session %u): nonce %llu (the caller's %llu), want %llu", (unsigned long long)i, sess[i],
+            (unsigned long long)got, (unsigned long long)(desc ? recs[i].nonce : got),
             (unsigned long long)want_nonce[i]);
     const uint32_t want_kill = want_st[i] == NOISE_GPU_REC_NONCE ? 0xffffffffu : sess[i];
-    CHECK(kill[i] == want_kill, "record %llu: refused mark %u", (unsigned long long)i, kill[i]);
+    CHECK(kill == want_kill, "record %llu: refused mark %u", (unsigned long long)i, kill);
     if (desc) {
       CHECK(recs[i].key_idx == sess[i] && recs[i].len == 0x77777777u && recs[i].in_off == 0x7777777777777777ull,
             "record %llu: descriptor fields besides the nonce changed", (unsigned long long)i);
+    } else {
+      CHECK(idx[i] == sess[i], "record %llu: the caller's index changed", (unsigned long long)i);
     }
   }
   CHECK(t.ctr == want_ctr, "counters differ from the loop's");
-  std::printf("ok %s: %llu records, %u sessions, %s\n", name, (unsigned long long)nrec, t.nsess,
-              desc ? "descriptors" : "arrays");
+  std::printf("ok %s: %llu records, %u sessions, %s%s\n", name, (unsigned long long)nrec, t.nsess,
+              desc ? "descriptors" : "arrays", decrypt ? ", decrypt" : "");
 }
 
 void key_rows(Table &t, std::mt19937_64 &rng, uint32_t keyless_every) {
@@ -190,6 +199,44 @@ void case_limit(const char *name, uint64_t nrec) {
   run_batch(name, t, sess, true);  // session 5: all refused now
 }
 
+// the decrypt direction, so that k_cs_fix runs: sessions at and next to the
+// nonce limit among the others, indices that are no session, keyless rows
+void case_decrypt(const char *name, uint64_t nrec) {
+  std::mt19937_64 rng(400 + nrec);
+  Table t(40);
+  key_rows(t, rng, 7);
+  for (auto &c : t.ctr) c = rng() >> 8;
+  t.ctr[1] = kLimit - 1;  // room for one record
+  t.ctr[2] = kLimit;      // for none
+  std::vector<uint32_t> sess(nrec);
+  for (uint64_t i = 0; i < nrec; ++i) {
+    sess[i] = i % 5 == 0 ? 1u + (uint32_t)(i / 5 % 2) : (uint32_t)(rng() % 40);
+    if (i % 37 == 6) sess[i] = 40 + (uint32_t)(i % 3);  // not a session
+    if (i % 91 == 8) sess[i] = 0xffffffffu;
+  }
+  sess[0] = 2;
+  run_batch(name, t, sess, false, true);
+  run_batch(name, t, sess, true, true);  // sessions 1 and 2: all refused now
+}
+
+// cs_scratch_layout against the four layouts the calls used to write out
+void case_layout(const char *name) {
+  for (uint64_t n : {1ull, 64ull, 65ull, 1500ull, 1ull << 20}) {
+    const size_t sort = align16(cs_assign_scratch_bytes(n)), commit = align16(cw_commit_scratch_bytes(n)),
+                 pre = align16(n), rec = sizeof(noise_gpu_record);
+    const CsScratchLayout a = cs_scratch_layout(false, true, n), b = cs_scratch_layout(false, false, n),
+                          c = cs_scratch_layout(true, true, n), d = cs_scratch_layout(true, false, n);
+    CHECK(!a.work && a.priv == sort && a.total == sort + rec * n, "sort | priv, %llu records", (unsigned long long)n);
+    CHECK(!b.work && b.nonces == sort && b.priv == sort + 8 * n && b.total == sort + 12 * n,
+          "sort | nonces | idx, %llu records", (unsigned long long)n);
+    CHECK(!c.work && c.pre == commit && c.priv == commit + pre && c.total == commit + pre + rec * n,
+          "commit | pre | priv, %llu records", (unsigned long long)n);
+    CHECK(!d.work && d.pre == commit && d.priv == commit + pre && d.total == commit + pre + 4 * n,
+          "commit | pre | idx, %llu records", (unsigned long long)n);
+  }
+  std::printf("ok %s\n", name);
+}
+
 void case_rekey(const char *name) {
   std::mt19937_64 rng(5);
   Table t(200);
@@ -234,6 +281,12 @@ int main() {
   case_mixed("nsess-70000", 70000, 5000, 4, 0);
   case_limit("limit-small", 60);
   case_limit("limit-sorted", 400);
+  for (uint64_t n : {1, 63, 64, 65, 129, 1500}) {
+    char name[64];
+    std::snprintf(name, sizeof name, "decrypt-%llu", (unsigned long long)n);
+    case_decrypt(name, n);
+  }
+  case_layout("layout");
   case_rekey("rekey");
   if (g_fail) {
     std::printf("%d failures\n", g_fail);

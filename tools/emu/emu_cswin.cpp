@@ -1,13 +1,15 @@
 // emu_cswin.cpp -- the replay-window kernels (cswin_kernels.hip, unmodified)
 // and the sort they share with nonce assignment (cstate_kernels.hip) on the CPU
 // under AddressSanitizer, checked against the plain loop of include/noise_gpu.h
-// over noise::ReplayWindow.  The AEAD between prefilter and commit is a
-// stand-in here (a per-record "tag verifies" flag; an accepted record's output
-// is filled with a pattern): what runs is the window logic, its statuses and
-// what it does to the outputs.  The build caps the grid at 3 workgroups and
-// cuts the sort into 640-record chunks; tables, batches, outputs and scratch
-// are allocated at their exact sizes, so an index past any of them is an ASan
-// report.
+// over noise::ReplayWindow.  A batch goes through the windowed call of
+// cstate_calls.hpp itself -- the scratch carve, the private copy, prefilter,
+// commit and finish -- as the C ABI runs it; only the AEAD launch between
+// prefilter and commit is a stand-in (a per-record "tag verifies" flag; an
+// accepted record's output is filled with a pattern), which also checks what
+// the prefilter left.  The build caps the grid at 3 workgroups and cuts the
+// sort into 640-record chunks; tables, batches and outputs are allocated at
+// their exact sizes and the scratch at cs_scratch_layout's total, so an index
+// past any of them or past a scratch region is an ASan report.
 //   emu_cswin            all cases
 #include <hip/hip_runtime.h>
 
@@ -17,7 +19,7 @@
 #include <random>
 #include <vector>
 
-#include "launchers.hpp"
+#include "cstate_calls.hpp"
 #include "noise_amd/replay_window.hpp"
 
 using namespace noise_amd;
@@ -82,7 +84,7 @@ struct Batch {
   std::vector<uint8_t> tag_ok;
 };
 
-// one windowed "decrypt": filter, the stand-in AEAD, commit, finish -- against the loop
+// one windowed "decrypt" through cs_window_call, around the stand-in AEAD -- against the loop
 void run_batch(const char *name, Table &t, const Batch &b, bool desc, unsigned need) {
   const uint64_t nrec = b.sess.size();
   // ---- expected: the plain loop, in record order
@@ -149,50 +151,42 @@ void run_batch(const char *name, Table &t, const Batch &b, bool desc, unsigned n
     }
   }
   std::vector<uint8_t> out(total, kCanary);
-  std::vector<uint32_t> kill(b.sess);
-  std::vector<uint8_t> pre(nrec, 0xA5), status(nrec, 0xA5);
-  CwBatch cb{};
-  if (desc) {
-    cb.sess = reinterpret_cast<const uint8_t *>(recs.data()) + offsetof(noise_gpu_record, key_idx);
-    cb.nonce = reinterpret_cast<const uint8_t *>(recs.data()) + offsetof(noise_gpu_record, nonce);
-    cb.sess_stride = cb.nonce_stride = sizeof(noise_gpu_record);
-  } else {
-    cb.sess = reinterpret_cast<const uint8_t *>(idx.data());
-    cb.sess_stride = 4;
-    cb.nonce = reinterpret_cast<const uint8_t *>(nonce.data());
-    cb.nonce_stride = 8;
-  }
-  cb.nrec = nrec;
+  std::vector<uint8_t> status(nrec, 0xA5);
+  const CsScratchLayout l = cs_scratch_layout(true, desc, nrec);
+  std::vector<uint8_t> scratch(l.total, 0xA5);
+  const uint8_t *pre = scratch.data() + l.pre;
 
-  // ---- filter: read-only on the table
+  // ---- the stand-in AEAD, after the prefilter (read-only on the table) and before the commit
   const std::vector<uint64_t> next0 = t.wnext;
   const std::vector<uint32_t> bits0 = t.wbits;
-  hipError_t e = launch_cw_filter(t.view(), t.win(), cb, pre.data(), reinterpret_cast<uint8_t *>(kill.data()),
-                                  4, nullptr);
-  CHECK(e == hipSuccess, "filter: launch error %d", (int)e);
-  CHECK(t.wnext == next0 && t.wbits == bits0, "the prefilter wrote to the table");
-  for (uint64_t i = 0; i < nrec; ++i) {
-    uint8_t p = want[i];
-    if (p == NOISE_GPU_REC_BAD_MAC || (p == NOISE_GPU_REC_REPLAY && in_batch[i])) p = 0;  // candidates
-    CHECK(pre[i] == p, "record %llu: pre-status %u, want %u", (unsigned long long)i, pre[i], p);
-    CHECK(kill[i] == (p ? 0xffffffffu : b.sess[i]), "record %llu: refused mark %u", (unsigned long long)i, kill[i]);
-  }
-  // ---- the stand-in AEAD: refused -> BAD_KEY, nothing written; bad tag -> BAD_MAC; else plaintext
-  for (uint64_t i = 0; i < nrec; ++i) {
-    if (kill[i] == 0xffffffffu) status[i] = NOISE_GPU_REC_BAD_KEY;
-    else if (!b.tag_ok[i]) status[i] = NOISE_GPU_REC_BAD_MAC;
-    else {
-      status[i] = NOISE_GPU_REC_OK;
-      std::memset(&out[off[i]], kPlain, len[i]);
+  bool between = false;
+  auto aead = [&](const CsColumns &mine) {
+    CHECK(t.wnext == next0 && t.wbits == bits0, "the prefilter wrote to the table");
+    for (uint64_t i = 0; i < nrec; ++i) {
+      uint8_t p = want[i];
+      if (p == NOISE_GPU_REC_BAD_MAC || (p == NOISE_GPU_REC_REPLAY && in_batch[i])) p = 0;  // candidates
+      uint32_t kill;
+      std::memcpy(&kill, mine.sess + i * mine.sess_stride, 4);
+      CHECK(pre[i] == p, "record %llu: pre-status %u, want %u", (unsigned long long)i, pre[i], p);
+      CHECK(kill == (p ? 0xffffffffu : b.sess[i]), "record %llu: refused mark %u", (unsigned long long)i, kill);
+      // refused -> BAD_KEY, nothing written; bad tag -> BAD_MAC; else plaintext
+      if (kill == 0xffffffffu) status[i] = NOISE_GPU_REC_BAD_KEY;
+      else if (!b.tag_ok[i]) status[i] = NOISE_GPU_REC_BAD_MAC;
+      else {
+        status[i] = NOISE_GPU_REC_OK;
+        std::memset(&out[off[i]], kPlain, len[i]);
+      }
     }
-  }
-  // ---- commit, finish
-  std::vector<uint8_t> scratch(cw_commit_scratch_bytes(nrec));
-  e = launch_cw_commit(t.view(), t.win(), cb, status.data(), scratch.data(), nullptr);
-  CHECK(e == hipSuccess, "commit: launch error %d", (int)e);
-  e = launch_cw_finish(pre.data(), status.data(), desc ? recs.data() : nullptr, out.data(), stride, len_u,
-                       nrec, nullptr);
-  CHECK(e == hipSuccess, "finish: launch error %d", (int)e);
+    between = true;
+  };
+  const hipError_t e = cs_window_call(
+      t.view(), t.win(), desc ? cs_columns(recs.data()) : cs_columns(idx.data(), nonce.data()), nrec,
+      scratch.data(), out.data(), stride, len_u, status.data(), nullptr, [&](const CsColumns &mine) {
+        aead(mine);
+        return hipSuccess;
+      });
+  if (!between) return;  // a CHECK of the stand-in's
+  CHECK(e == hipSuccess, "launch error %d", (int)e);
   for (uint64_t i = 0; i < nrec; ++i)
     CHECK(status[i] == want[i], "record %llu (session %u, nonce %llu): status %u, want %u",
           (unsigned long long)i, b.sess[i], (unsigned long long)b.nonce[i], status[i], want[i]);
