@@ -20,6 +20,11 @@
 //       through the batched GPU handshake with preset keys and random
 //       payloads vs the host HandshateState per session (every message), plus
 //       tampered messages failing exactly their sessions
+//   handshake_test batch_edges <pattern> [edges.tsv]  96 sessions with prologue
+//       and payload lengths at the BLAKE2b block and AEAD step boundaries, the
+//       largest message, unaligned spans, EVERY session vs the host
+//       HandshakeState; on NN and XX also message 1 with low-order and
+//       small-output ephemerals from tests/golden/x25519_edge_vectors.tsv
 //   handshake_test batch_bench <pattern> <n> <reps>  full handshakes/s of
 //       the batched GPU handshake (fresh DRBG ephemerals, empty payloads)
 #include <algorithm>
@@ -240,17 +245,20 @@ struct Dev {
   template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
-// Ragged per-session buffers packed at 16-byte aligned offsets on the device
+// Ragged per-session buffers packed at 16-byte aligned offsets on the device;
+// skew >= 0: session i's offset is moved (i + skew) % 8 bytes off that
+// alignment (batch_edges: every residue mod 8, the byte-wise paths)
 struct Ragged {
   std::vector<std::uint64_t> off;
   std::vector<std::uint32_t> len;
   std::unique_ptr<Dev> data, doff, dlen;
-  Ragged(const std::vector<bytes> &items, std::size_t room) {
+  Ragged(const std::vector<bytes> &items, std::size_t room, int skew = -1) {
     std::uint64_t o = 0;
     for (const bytes &b : items) {
-      off.push_back(o);
+      const std::uint64_t sk = skew >= 0 ? (off.size() + (std::size_t)skew) % 8 : 0;
+      off.push_back(o + sk);
       len.push_back((std::uint32_t)b.size());
-      o += (b.size() + room + 15) & ~std::size_t(15);
+      o += (sk + b.size() + room + 15) & ~std::size_t(15);
     }
     data = std::make_unique<Dev>(o);
     std::vector<std::uint8_t> h(o ? o : 1, 0);
@@ -288,7 +296,7 @@ struct RoleKeys {
 };
 
 static void set_role(BatchSide &b, const std::string &pattern, bool init, const RoleKeys &k,
-                     std::size_t n) {
+                     std::size_t n, int skew = -1) {
   HSCHK(noise_gpu_hs_create(pattern.c_str(), init, n, &b.hs));
   auto put_keys = [&](int slot, const std::vector<bytes> &v) {
     if (v.empty() || v[0].empty()) return;
@@ -311,7 +319,7 @@ static void set_role(BatchSide &b, const std::string &pattern, bool init, const 
     HSCHK(noise_gpu_hs_set_psks(b.hs, d.p, nullptr));
     HIPCHK(hipDeviceSynchronize());
   }
-  Ragged pro(k.prologue, 0);
+  Ragged pro(k.prologue, 0, skew);
   noise_gpu_span ps = pro.span();
   HSCHK(noise_gpu_hs_start(b.hs, &ps, nullptr));
   HIPCHK(hipDeviceSynchronize());
@@ -321,12 +329,13 @@ static void set_role(BatchSide &b, const std::string &pattern, bool init, const 
 // messages; received payloads and per-session status into *got / *status.
 static std::vector<bytes> batch_message(BatchSide &w, BatchSide &r, const std::vector<bytes> &payloads,
                                         std::vector<bytes> *got, std::vector<std::uint8_t> *status,
-                                        const std::vector<std::pair<std::size_t, std::size_t>> &tamper = {}) {
+                                        const std::vector<std::pair<std::size_t, std::size_t>> &tamper = {},
+                                        int skew = -1) {
   const std::size_t n = payloads.size();
   noise_gpu_hs_info info;
   HSCHK(noise_gpu_hs_info_get(w.hs, &info));
-  Ragged pay(payloads, 0);
-  Ragged msg(payloads, info.overhead);
+  Ragged pay(payloads, 0, skew);
+  Ragged msg(payloads, info.overhead, skew < 0 ? -1 : skew + 3);
   Dev mlen(4 * n);
   noise_gpu_span ps = pay.span(), ms = msg.span();
   HSCHK(noise_gpu_hs_write_message(w.hs, &ps, &ms, mlen.as<std::uint32_t>(), nullptr));
@@ -345,7 +354,7 @@ static std::vector<bytes> batch_message(BatchSide &w, BatchSide &r, const std::v
     HIPCHK(hipMemcpy(msg.data->p + msg.off[i] + byte, &v, 1, hipMemcpyHostToDevice));
   }
   msg.dlen->put(ml.data(), 4 * n);
-  Ragged out(payloads, 16);
+  Ragged out(payloads, 16, skew < 0 ? -1 : skew + 5);
   Dev plen(4 * n), st(n);
   noise_gpu_span ms2 = msg.span(), os = out.span();
   HSCHK(noise_gpu_hs_read_message(r.hs, &ms2, &os, plen.as<std::uint32_t>(), st.p, nullptr));
@@ -619,6 +628,244 @@ static int run_batch_check(const std::string &pattern, std::size_t n, unsigned s
   return 0;
 }
 
+// ---- batch_edges ------------------------------------------------------------
+// BLAKE2b block boundaries, long messages, unaligned spans and degenerate DH
+// outputs in the batched handshake, EVERY session against the host
+// HandshakeState: each message, the handshake hash, both split keys.
+//  * prologue lengths from kEdgePro: 64 + len = 127/128/129, 255/256/257 and a
+//    multi-block run (mix_hash_mem's block count and last flag);
+//  * payload lengths from kEdgePay: with and without the tag 64 + ct_len lies
+//    on both sides of 128 and 256, the AEAD on both sides of its 16- and
+//    64-byte steps;
+//  * two sessions carry the largest payload that fits a 65535-byte message,
+//    one on the first keyed payload, one on the first unkeyed one (if the
+//    pattern has one); the bytes are compared;
+//  * prologue, payload and message spans sit at offsets of every residue
+//    mod 8 (load_word's aligned and byte-wise branches, the clipped last word);
+//  * NN and XX, second phase: message 1's e replaced per session by a
+//    low-order u (ee = 0) or by a point that the session's preset responder
+//    ephemeral maps to 2, 9 or 16 (k_hs_dh's scalarmult subtracting p in
+//    fe_tobytes), both from tests/golden/x25519_edge_vectors.tsv; the GPU
+//    responder's status and message 2 -- for NN, which ends there, the hash
+//    and the split keys too -- against the host responder fed the same bytes.
+static const std::size_t kEdgePro[] = {0, 1, 63, 64, 65, 127, 128, 191, 192, 193, 1000};
+static const std::size_t kEdgePay[] = {0, 1, 15, 16, 17, 47, 48, 49, 63, 64, 65, 111, 112, 113, 175, 176, 177, 239, 240, 241};
+
+// HasKey() when each message's payload is encrypted (rev34 §5.3: MixKey at
+// every DH and psk token, and at e in psk mode)
+static std::vector<bool> payload_keyed(const noise::detail::PatternProgram &prog) {
+  std::vector<bool> out;
+  bool key = false;
+  for (const auto &msg : prog.msgs) {
+    for (PatternToken t : msg) key = key || (t != PatternToken::S && (t != PatternToken::E || prog.psk_mode));
+    out.push_back(key);
+  }
+  return out;
+}
+
+// both split keys of a host HandshakeState against the GPU's key rows: the
+// same 64 bytes encrypted under each must agree
+static void check_split(noise::HandshakeState &h, const std::array<std::uint8_t, 32> &k1,
+                        const std::array<std::uint8_t, 32> &k2, std::size_t i) {
+  auto [c1, c2] = h.finalize();
+  noise::CipherState *host[2] = {&c1, &c2};
+  const std::array<std::uint8_t, 32> *gpu[2] = {&k1, &k2};
+  for (int j = 0; j < 2; ++j) {
+    bytes a(64, (std::uint8_t)(7 + j)), b = a;
+    host[j]->encrypt_with_ad(a);
+    noise::CipherState g;
+    g.initialize_key(*gpu[j]);
+    g.encrypt_with_ad(b);
+    if (a != b) throw std::runtime_error("split key k" + std::to_string(j + 1) + " differs from the host, session " + std::to_string(i));
+  }
+}
+
+struct EdgeVec {
+  std::array<std::uint8_t, 32> sk, u, out;
+};
+
+static int run_batch_edges(const std::string &pattern, const char *fixture) {
+  const std::size_t n = 96;  // a full wave and a partial one
+  std::mt19937_64 g(0xed9e5 + pattern.size() * 131 + (unsigned char)pattern[0]);
+  const noise::detail::PatternProgram prog = noise::detail::parse_pattern(pattern);
+  auto pre_has = [](const std::vector<PatternToken> &t, PatternToken x) {
+    for (PatternToken y : t) if (y == x) return true;
+    return false;
+  };
+  RoleKeys ki, kr;
+  std::vector<noise::KeyPair> si(n), sr(n), ei(n), er(n);
+  std::vector<noise::HandshakeStateConfiguration> ci(n), cr(n);
+  for (std::size_t i = 0; i < n; ++i) {
+    std::array<std::uint8_t, 32> a;
+    for (auto *kp : {&si[i], &sr[i], &ei[i], &er[i]}) {
+      for (auto &x : a) x = (std::uint8_t)g();
+      *kp = noise::keypair_from_private(a);
+    }
+    const bytes pro = rand_bytes(g, kEdgePro[i % 11]);
+    ki.prologue.push_back(pro);
+    kr.prologue.push_back(pro);
+    ki.s.emplace_back(si[i].sk.begin(), si[i].sk.end());
+    kr.s.emplace_back(sr[i].sk.begin(), sr[i].sk.end());
+    ki.e.emplace_back(ei[i].sk.begin(), ei[i].sk.end());
+    kr.e.emplace_back(er[i].sk.begin(), er[i].sk.end());
+    std::vector<bytes> psks;
+    for (std::size_t p = 0; p < prog.npsk; ++p) psks.push_back(rand_bytes(g, 32));
+    ki.psks.push_back(psks);
+    kr.psks.push_back(psks);
+    ki.rs.push_back(pre_has(prog.pre_r, PatternToken::S) ? bytes(sr[i].pk.begin(), sr[i].pk.end()) : bytes());
+    kr.rs.push_back(pre_has(prog.pre_i, PatternToken::S) ? bytes(si[i].pk.begin(), si[i].pk.end()) : bytes());
+    ci[i].initiator = true;
+    cr[i].initiator = false;
+    ci[i].prologue = cr[i].prologue = pro;
+    ci[i].s = si[i];
+    cr[i].s = sr[i];
+    ci[i].e = ei[i];
+    cr[i].e = er[i];
+    if (!ki.rs[i].empty()) ci[i].rs = sr[i].pk;
+    if (!kr.rs[i].empty()) cr[i].rs = si[i].pk;
+    ci[i].psks = cr[i].psks = psks;
+  }
+  // ---- phase 1: whole handshakes, every session against the host -----------
+  std::size_t messages = 0, big_keyed = 0, big_unkeyed = 0;
+  {
+    std::vector<std::unique_ptr<noise::HandshakeState>> hi(n), hr(n);
+    for (std::size_t i = 0; i < n; ++i) {
+      hi[i] = std::make_unique<noise::HandshakeState>();
+      hr[i] = std::make_unique<noise::HandshakeState>();
+      hi[i]->initialize_named(pattern, ci[i]);
+      hr[i]->initialize_named(pattern, cr[i]);
+    }
+    BatchSide bi, br;
+    set_role(bi, pattern, true, ki, n, 1);
+    set_role(br, pattern, false, kr, n, 4);
+    const std::vector<bool> keyed = payload_keyed(prog);
+    const std::size_t kBigKeyed = 5, kBigUnkeyed = n - 3;
+    bool had_keyed = false, had_unkeyed = false;
+    for (std::size_t m = 0; m < prog.msgs.size(); ++m) {
+      const bool init_sends = prog.one_way || m % 2 == 0;
+      BatchSide &w = init_sends ? bi : br, &r = init_sends ? br : bi;
+      noise_gpu_hs_info info;
+      HSCHK(noise_gpu_hs_info_get(w.hs, &info));
+      std::vector<bytes> payloads(n), got;
+      for (std::size_t i = 0; i < n; ++i) payloads[i] = rand_bytes(g, kEdgePay[(i + 7 * m) % 20]);
+      if (keyed[m] && !had_keyed) {
+        payloads[kBigKeyed] = rand_bytes(g, 65535 - info.overhead);
+        had_keyed = true;
+        ++big_keyed;
+      } else if (!keyed[m] && !had_unkeyed) {
+        payloads[kBigUnkeyed] = rand_bytes(g, 65535 - info.overhead);
+        had_unkeyed = true;
+        ++big_unkeyed;
+      }
+      std::vector<std::uint8_t> st;
+      const std::vector<bytes> wire = batch_message(w, r, payloads, &got, &st, {}, (int)(2 * m));
+      for (std::size_t i = 0; i < n; ++i) {
+        const std::string where = "message " + std::to_string(m) + ", session " + std::to_string(i) + " (prologue " +
+                                  std::to_string(ki.prologue[i].size()) + " B, payload " +
+                                  std::to_string(payloads[i].size()) + " B)";
+        if (st[i] || got[i] != payloads[i]) throw std::runtime_error("payload not recovered: " + where);
+        noise::HandshakeState &hw = init_sends ? *hi[i] : *hr[i], &hrd = init_sends ? *hr[i] : *hi[i];
+        bytes p = payloads[i], out, back;
+        hw.write_message(p, out);
+        if (out != wire[i]) throw std::runtime_error("differs from the host: " + where);
+        hrd.read_message(out, back);
+        if (back != payloads[i]) throw std::runtime_error("the host did not recover the payload: " + where);
+        ++messages;
+      }
+    }
+    const SplitOut oi = batch_split(bi, n), orr = batch_split(br, n);
+    for (std::size_t i = 0; i < n; ++i) {
+      if (oi.k1[i] != orr.k1[i] || oi.k2[i] != orr.k2[i] || oi.hash[i] != orr.hash[i])
+        throw std::runtime_error("sides disagree, session " + std::to_string(i));
+      if (hi[i]->get_handshake_hash() != oi.hash[i] || hr[i]->get_handshake_hash() != oi.hash[i])
+        throw std::runtime_error("handshake hash differs from the host, session " + std::to_string(i));
+      check_split(*hi[i], oi.k1[i], oi.k2[i], i);
+    }
+  }
+  // ---- phase 2: tampered ephemerals (NN, XX) -------------------------------
+  std::size_t low = 0, small = 0;
+  if (pattern == "NN" || pattern == "XX") {
+    std::vector<EdgeVec> lows, smalls;
+    std::ifstream in(fixture ? fixture : "");
+    std::string line;
+    while (std::getline(in, line)) {
+      std::istringstream is(line);
+      std::string a, b, c, cls;
+      if (!(is >> a >> b >> c >> cls) || a[0] == '#' || a.size() != 64) continue;
+      const EdgeVec v{a32(a), a32(b), a32(c)};
+      if (cls == "low_order") lows.push_back(v);
+      if (cls == "small_out") smalls.push_back(v);
+    }
+    if (lows.size() < 16 || smalls.size() < 48) throw std::runtime_error("edge fixture missing or without its classes");
+    std::vector<bytes> msg1(n), pay1(n);
+    std::vector<noise::KeyPair> e2(n);
+    RoleKeys k2 = kr;
+    for (std::size_t i = 0; i < n; ++i) {
+      const EdgeVec &v = i % 2 ? smalls[(i / 2) % smalls.size()] : lows[(i / 2 * 5) % lows.size()];
+      e2[i] = noise::keypair_from_private(v.sk);  // the responder's ephemeral: the vector's scalar
+      k2.e[i].assign(v.sk.begin(), v.sk.end());
+      pay1[i] = rand_bytes(g, kEdgePay[(i + 3) % 20]);
+      msg1[i].assign(v.u.begin(), v.u.end());
+      msg1[i].insert(msg1[i].end(), pay1[i].begin(), pay1[i].end());
+      // what ee must be: the vector's output (0 for a low-order u)
+      if (noise::crypto::x25519(v.sk, v.u) != v.out) throw std::runtime_error("host X25519 differs from the fixture, session " + std::to_string(i));
+      (i % 2 ? small : low) += 1;
+    }
+    BatchSide br;
+    set_role(br, pattern, false, k2, n, 2);
+    Ragged msg(msg1, 0, 6), out(pay1, 16, 3);
+    Dev plen(4 * n), st(n);
+    noise_gpu_span ms = msg.span(), os = out.span();
+    HSCHK(noise_gpu_hs_read_message(br.hs, &ms, &os, plen.as<std::uint32_t>(), st.p, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<std::uint8_t> sv(n);
+    std::vector<std::uint32_t> pl(n);
+    st.get(sv.data(), n);
+    plen.get(pl.data(), 4 * n);
+    std::vector<bytes> pay2(n);
+    for (auto &p : pay2) p = rand_bytes(g, kEdgePay[g() % 20]);
+    noise_gpu_hs_info info;
+    HSCHK(noise_gpu_hs_info_get(br.hs, &info));
+    Ragged p2(pay2, 0, 5), m2(pay2, info.overhead, 0);
+    Dev mlen(4 * n);
+    noise_gpu_span ps2 = p2.span(), ms2 = m2.span();
+    HSCHK(noise_gpu_hs_write_message(br.hs, &ps2, &ms2, mlen.as<std::uint32_t>(), nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<std::uint32_t> ml(n);
+    mlen.get(ml.data(), 4 * n);
+    Dev st2(n);
+    HSCHK(noise_gpu_hs_status(br.hs, st2.p, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<std::uint8_t> sv2(n);
+    st2.get(sv2.data(), n);
+    std::vector<std::unique_ptr<noise::HandshakeState>> hr(n);
+    for (std::size_t i = 0; i < n; ++i) {
+      const std::string where = "tampered e, session " + std::to_string(i);
+      noise::HandshakeStateConfiguration c = cr[i];
+      c.e = e2[i];
+      hr[i] = std::make_unique<noise::HandshakeState>();
+      hr[i]->initialize_named(pattern, c);
+      bytes m = msg1[i], back, p = pay2[i], wire;
+      hr[i]->read_message(m, back);  // neither the reference nor the host rejects such keys
+      if (sv[i] != 0 || sv2[i] != 0) throw std::runtime_error("the GPU responder failed where the host did not: " + where);
+      if (pl[i] != pay1[i].size() || out.item(i, pl[i]) != back) throw std::runtime_error("payload 1 differs from the host: " + where);
+      hr[i]->write_message(p, wire);
+      if (ml[i] != wire.size() || m2.item(i, ml[i]) != wire) throw std::runtime_error("message 2 differs from the host: " + where);
+    }
+    if (pattern == "NN") {  // two messages: the responder is finished
+      const SplitOut o = batch_split(br, n);
+      for (std::size_t i = 0; i < n; ++i) {
+        if (hr[i]->get_handshake_hash() != o.hash[i]) throw std::runtime_error("handshake hash differs from the host: tampered e, session " + std::to_string(i));
+        check_split(*hr[i], o.k1[i], o.k2[i], i);
+      }
+    }
+  }
+  std::printf("batch_edges %s n=%zu: %zu messages, %zu hashes and key pairs against the host, largest message keyed %zu "
+              "unkeyed %zu, tampered e: %zu low-order %zu small-output: ok\n", pattern.c_str(), n, messages, n,
+              big_keyed, big_unkeyed, low, small);
+  return 0;
+}
+
 // Full handshakes/s: both roles of `pattern` for n sessions, fresh DRBG
 // ephemerals, empty payloads, random statics (one per side, stride 0: a
 // server key and a client key), all on one stream.
@@ -714,6 +961,8 @@ int main(int argc, char **argv) {
       return run_batch_vectors(argv[2]);
     } else if (cmd == "batch_check" && argc == 5) {
       return run_batch_check(argv[2], std::stoul(argv[3]), (unsigned)std::stoul(argv[4]));
+    } else if (cmd == "batch_edges" && (argc == 3 || argc == 4)) {
+      return run_batch_edges(argv[2], argc == 4 ? argv[3] : nullptr);
     } else if (cmd == "batch_bench" && argc == 5) {
       return run_batch_bench(argv[2], std::stoul(argv[3]), std::atoi(argv[4]));
     } else if (cmd == "loopback" && argc == 4) {

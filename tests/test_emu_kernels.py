@@ -9,7 +9,10 @@ offsets whose low word has bit 31 set); "ragged" lengths 1..70000 give odd
 segment tails and > 65535-byte records (generic class); a 300-segment
 scratch cap forces the segment-overflow path.  Test infrastructure only: the
 product runs these kernels on the GPU (tests/test_gpu_records_mixed.py).
-The batched-handshake kernels run the same way (emu_handshake)."""
+The batched-handshake kernels run the same way (emu_handshake, and
+emu_handshake_edges: tests/cpp/handshake_test.cpp's batch_edges mode); the
+X25519 device header and the host's X25519 run on crafted edge vectors
+(emu_x25519_edges)."""
 import os
 import subprocess
 
@@ -48,6 +51,11 @@ TRANSPORT_CASES = [
     ["pipeline_batch", "40", "4500", "8", "8192", str(64 << 10), "1500", "20000", "96", "0"],
 ]
 BUILD = os.path.join(EMU, "build")
+X25519_EDGES = os.path.join(ROOT, "tests", "golden", "x25519_edge_vectors.tsv")
+# handshake_test batch_edges in the emulation (~2 min each beside the other
+# runs): the two patterns with the tampered-ephemeral phase; the GPU suite
+# runs five (tests/test_gpu_handshake_batch.py)
+HS_EDGE_PATTERNS = ["XX", "NN"]
 ASAN_NOLEAK = "detect_leaks=0:allocator_may_return_null=1"
 
 
@@ -76,7 +84,12 @@ def _job_list():
                                     900 if i == 5 else 600)
     jobs["handshake"] = ([os.path.join(BUILD, "emu_handshake"),
                           os.path.join(ROOT, "tests", "golden", "handshake_vectors.tsv")], "detect_leaks=0", 900)
+    for pattern in HS_EDGE_PATTERNS:
+        jobs["hs-edges-" + pattern] = ([os.path.join(BUILD, "emu_handshake_edges"), "batch_edges", pattern,
+                                        X25519_EDGES], "detect_leaks=0", 900)
     jobs["x25519"] = ([os.path.join(BUILD, "emu_x25519"), "300", "11"], "detect_leaks=0", 300)
+    # a fourth entry: the file the run reads on its standard input
+    jobs["x25519-edges"] = ([os.path.join(BUILD, "emu_x25519_edges")], "detect_leaks=0", 300, X25519_EDGES)
     return jobs
 
 
@@ -91,18 +104,20 @@ def emu():
     _make("GRID_CAP=3u", "uniform")
     _make("GRID_CAP=3u", "transport")
     _make("handshake")
+    _make("GRID_CAP=3u", "hsedges")
     jobs = _job_list()
 
     logs = os.path.join(BUILD, "logs")
     os.makedirs(logs, exist_ok=True)
 
     def run(name):
-        argv, asan, timeout = jobs[name]
+        argv, asan, timeout = jobs[name][:3]
         # the whole output stays in build/logs/<name>.log (the assertion
         # messages carry only its tail; emu_api's watchdog lines and phase
         # times go there)
-        with open(os.path.join(logs, name + ".log"), "w") as f:
-            r = subprocess.run(argv, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+        with open(os.path.join(logs, name + ".log"), "w") as f, \
+                open(jobs[name][3] if len(jobs[name]) > 3 else os.devnull) as stdin:
+            r = subprocess.run(argv, stdin=stdin, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                                timeout=timeout, env=dict(os.environ, ASAN_OPTIONS=asan))
             f.write(r.stdout)
             f.write(r.stderr)
@@ -209,12 +224,90 @@ def test_emulated_batched_handshakes(emu):
     assert "vectors 110, failed 0" in r.stdout and "transport records 211" in r.stdout, r.stdout
 
 
+@pytest.mark.parametrize("pattern", HS_EDGE_PATTERNS)
+def test_emulated_batched_handshake_edges(emu, pattern):
+    """tests/cpp/handshake_test.cpp batch_edges, unmodified, over the emulated
+    kernels under ASan: prologue and payload lengths at every BLAKE2b block
+    boundary of h || data, 65535-byte messages, spans at every offset mod 8,
+    and message 1 with low-order and small-output ephemerals -- every session
+    against the host HandshakeState (messages, hash, both split keys), and no
+    load or store outside a span."""
+    r = _result(emu, "hs-edges-" + pattern)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
+    assert r.stdout.rstrip().endswith(": ok"), r.stdout
+    assert "largest message keyed 1 unkeyed 1, tampered e: 48 low-order 48 small-output" in r.stdout, r.stdout
+
+
 def test_emulated_fixed_base_public_keys(emu):
     """x25519_device.hpp's fixed-base path (edwards25519 radix-16 table,
     constant-time selects) on the CPU under ASan: RFC 7748 §6.1 and random /
     extreme scalars against the device ladder with u = 9 and the host X25519."""
     r = _result(emu, "x25519")
     assert r.returncode == 0 and "0 failures: ok" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+def _edge_vectors():
+    """Section 1 of the edge fixture: (scalar, u, expected, class) per line."""
+    rows = []
+    for line in open(X25519_EDGES):
+        tok = line.split()
+        if len(tok) == 4 and not line.startswith("#"):
+            rows.append((bytes.fromhex(tok[0]), bytes.fromhex(tok[1]), bytes.fromhex(tok[2]), tok[3]))
+    return rows
+
+
+def test_emulated_x25519_edge_vectors(emu):
+    """x25519_device.hpp (scalarmult, base_scalarmult, the field operations)
+    and the host's noise::crypto::x25519 with its 51-bit field functions on
+    tests/golden/x25519_edge_vectors.tsv, under ASan + UBSan, every result
+    against the fixture's expected value.  The final conditional subtraction
+    of both fe_tobytes (q = 1) must run for every small_out vector (outputs 2,
+    9, 16: h = p + r, 19 q added and carried through limbs that are not all
+    ones) and, in every class, exactly for the vectors whose output is below
+    19; near_out, limb_edges and base_point have none.  (An all-zero output
+    comes from h = p, q = 1 too: the low_order vectors and u = p, p + 1.)  The
+    field operations at the derived limb bound (make_x25519_edges.py) all give
+    the canonical value: no overflow in 19 g, 38 f or a column sum."""
+    r = _result(emu, "x25519-edges")
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
+    assert "ok (0 failures)" in r.stdout
+    rows = _edge_vectors()
+    got = {}
+    for line in r.stdout.splitlines():
+        if line.startswith("class "):
+            w = line.replace(":", "").replace(",", "").split()
+            got[w[1]] = (int(w[3]), int(w[10]), int(w[14]))  # vectors, q = 1 device, q = 1 host
+    want = {}
+    for _, _, exp, cls in rows:
+        n, q = want.get(cls, (0, 0))
+        want[cls] = (n + 1, q + (int.from_bytes(exp, "little") < 19))
+    assert set(got) == set(want) == {"small_out", "near_out", "noncanonical", "low_order", "limb_edges",
+                                      "base_point"}
+    for cls, (n, q) in want.items():
+        assert got[cls] == (n, q, q), (cls, got[cls], n, q)
+    n_small = want["small_out"][0]
+    assert n_small >= 48 and got["small_out"] == (n_small, n_small, n_small)
+    for cls in ("near_out", "limb_edges", "base_point"):
+        assert got[cls][1:] == (0, 0), cls
+    # q = 1 outside small_out is h = p alone: an all-zero output
+    for _, _, exp, cls in rows:
+        assert cls == "small_out" or int.from_bytes(exp, "little") == 0 or int.from_bytes(exp, "little") >= 19
+    ops = [l for l in r.stdout.splitlines() if l.startswith("field operations ")]
+    assert ops and int(ops[0].split()[2].rstrip(",")) >= 200 and int(ops[0].split()[-1]) >= 50, r.stdout
+    base = [l for l in r.stdout.splitlines() if "through base_scalarmult" in l]
+    assert base and int(base[0].split()[-1]) >= 16, r.stdout
+
+
+def test_x25519_edge_fixture_is_current():
+    """tests/golden/x25519_edge_vectors.tsv is what make_x25519_edges.py
+    (Python big integers, every expected value computed by two ladders and
+    asserted) generates."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(
+        "make_x25519_edges", os.path.join(ROOT, "tests", "golden", "make_x25519_edges.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    assert mod.render()[0] == open(X25519_EDGES).read()
 
 
 def test_base_table_generator_is_current():

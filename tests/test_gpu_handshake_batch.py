@@ -12,7 +12,9 @@ csrc/handshake_kernels.hip; SURVEY.md §8(f) rank 4, mass handshakes).
 * XX on random keys for every session against the reference's own Monocypher
   primitives (oracle/_ref: ref_xx_handshake), and the split keys feeding the
   sessions transport kernel directly on the device;
-* length checks (short messages fail their sessions with HS_BAD_LEN)."""
+* length checks (short messages fail their sessions with HS_BAD_LEN);
+* batch_edges: BLAKE2b block boundaries, 65535-byte messages, unaligned spans
+  and low-order / small-output ephemerals, every session against the host."""
 import os
 import subprocess
 
@@ -53,6 +55,28 @@ def test_batch_vectors():
 def test_batch_vs_host_handshake(pattern, n):
     out = run("batch_check", pattern, n, n + 11)
     assert "ok" in out, out
+
+
+@pytest.mark.parametrize("pattern,tampered", [("XX", True), ("IK", False), ("NNpsk0+psk2", False),
+                                              ("N", False), ("NN", True)])
+def test_batch_edges_every_session_vs_host(pattern, tampered):
+    """tests/cpp/handshake_test.cpp batch_edges: 96 sessions whose prologue
+    and payload lengths put BLAKE2b's h || data on both sides of every block
+    boundary (64 + len = 127/128/129, 255/256/257, a multi-block run) and the
+    AEAD on both sides of its 16- and 64-byte steps, two 65535-byte messages
+    whose bytes are compared, spans at every offset mod 8 -- EVERY session
+    against the host HandshakeState: each message, the handshake hash, both
+    split keys.  On NN and XX also message 1 with e replaced by low-order u
+    (ee = 0) and by points that the responder's ephemeral maps to 2, 9 and 16
+    (tests/golden/x25519_edge_vectors.tsv): the GPU responder against the
+    host responder fed the same bytes."""
+    out = run("batch_edges", pattern, os.path.join(ROOT, "tests", "golden", "x25519_edge_vectors.tsv"))
+    assert out.rstrip().endswith(": ok"), out
+    nmsg = {"XX": 3, "IK": 2, "NNpsk0+psk2": 2, "N": 1, "NN": 2}[pattern]
+    assert "n=96: %d messages, 96 hashes and key pairs against the host" % (96 * nmsg) in out, out
+    # every pattern has a keyed payload; only XX and NN have an unkeyed one
+    assert "largest message keyed 1 unkeyed %d" % (pattern in ("XX", "NN")) in out, out
+    assert ("tampered e: 48 low-order 48 small-output" if tampered else "tampered e: 0 low-order 0 small-output") in out
 
 
 def _dev(b):

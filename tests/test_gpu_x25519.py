@@ -2,7 +2,9 @@
 noise_gpu_x25519) against RFC 7748 (§5.2 and §6.1 test vectors) and the
 independent pure-Python ladder of tests/golden/make_fixtures.py, on random
 scalars and u-coordinates including non-canonical ones (u >= p, bit 255 set,
-u = 0, 1, p-1).  Bit-exact."""
+u = 0, 1, p-1), and on the crafted edge vectors of
+tests/golden/x25519_edge_vectors.tsv (outputs below 19, low-order and
+non-canonical u, limb and word boundaries).  Bit-exact."""
 import os
 import random
 import sys
@@ -90,6 +92,54 @@ def test_vs_reference_monocypher():
         out = ctypes.create_string_buffer(32)
         ref.ref_x25519(out, sc[i], pts[i])
         assert got[i] == out.raw, "lane %d" % i
+
+
+def test_edge_vectors_one_launch():
+    """tests/golden/x25519_edge_vectors.tsv (make_x25519_edges.py) in one
+    launch, byte-exact: outputs 2, 9 and 16, the only ones for which
+    fe_tobytes subtracts p from h = p + r with r != 0; their neighbours 21, 31,
+    34, 35; every non-canonical u; every low-order u; u and scalars at the
+    limb and word boundaries.  The lanes are dealt round-robin over the
+    classes, so the small outputs share their waves with ordinary lanes.  The
+    u = 9 lines also go through the fixed-base path (no points), and where
+    oracle/_ref is built the reference's own crypto_x25519 confirms the
+    fixture."""
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "x25519_edge_vectors.tsv")
+    by_class = {}
+    for line in open(path):
+        tok = line.split()
+        if len(tok) == 4 and not line.startswith("#"):
+            by_class.setdefault(tok[3], []).append(tuple(bytes.fromhex(t) for t in tok[:3]))
+    small = [int.from_bytes(e, "little") for _, _, e in by_class["small_out"]]
+    for out in (2, 9, 16):
+        assert small.count(out) >= 16, "the fixture lost its small outputs"
+    assert len(small) == sum(small.count(o) for o in (2, 9, 16))
+    for cls in ("near_out", "noncanonical", "low_order", "limb_edges", "base_point"):
+        assert by_class[cls], cls
+    queues = [list(v) for _, v in sorted(by_class.items())]
+    lanes = []
+    while any(queues):
+        for q in queues:
+            if q:
+                lanes.append(q.pop(0))
+    assert 300 <= len(lanes) <= 512
+    where = [i for i, (_, _, e) in enumerate(lanes) if 0 < int.from_bytes(e, "little") < 19]
+    assert len({i // 64 for i in where}) >= 3 and len(where) < len(lanes) // 4
+    got = gpu_x25519([s for s, _, _ in lanes], [u for _, u, _ in lanes])
+    for i, (s, u, e) in enumerate(lanes):
+        assert got[i] == e, "lane %d: scalar %s u %s" % (i, s.hex(), u.hex())
+    base = by_class["base_point"]
+    pub = gpu_x25519([s for s, _, _ in base], None)
+    for i, (s, u, e) in enumerate(base):
+        assert u == (9).to_bytes(32, "little") and pub[i] == e, "fixed base, lane %d: scalar %s" % (i, s.hex())
+    ref_path = os.path.join(noise_amd.ROOT, "oracle", "_ref", "libnoise_ref.so")
+    if os.path.exists(ref_path):
+        import ctypes
+        ref = ctypes.CDLL(ref_path)
+        for i, (s, u, e) in enumerate(lanes):
+            out = ctypes.create_string_buffer(32)
+            ref.ref_x25519(out, s, u)
+            assert out.raw == e, "the reference disagrees with the fixture, lane %d" % i
 
 
 def test_ragged_count_and_alignment_check():
