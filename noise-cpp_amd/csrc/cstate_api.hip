@@ -23,12 +23,6 @@ struct noise_gpu_cs {
 
 namespace {
 
-#define CS_TRY(expr)                                          \
-  do {                                                        \
-    hipError_t e_ = (expr);                                   \
-    if (e_ != hipSuccess) return api_hip_fail(e_, #expr);     \
-  } while (0)
-
 constexpr uint64_t kCsMaxSess = 0xfffffffeull;  // 2^32-2: 0xffffffff marks a refused record
 constexpr uint64_t kCsMaxRec = 1ull << 31;
 constexpr uint64_t kCsWinRow = NOISE_GPU_CS_WINDOW / 8;  // bytes of a session's bitmap
@@ -178,7 +172,7 @@ int cs_records(bool decrypt, noise_gpu_cs *cs, noise_gpu_record *d_recs, uint64_
   const int rc = cs_check_records(cs, decrypt, d_recs, nrec, d_in, d_out, d_status);
   if (rc || nrec == 0) return rc;
   const hipStream_t st = (hipStream_t)stream;
-  CS_TRY(cs_scratch(cs, cs_scratch_layout(false, true, nrec).total, st));
+  API_TRY(cs_scratch(cs, cs_scratch_layout(false, true, nrec).total, st));
   return cs_done(cs_inorder_call(
       decrypt, cs->t, cs_columns(d_recs), nrec, cs->scratch, d_status, st, [&](const CsColumns &mine) {
         return launch_aead_records(decrypt, cs->t.keys, cs->t.nsess, mine.recs, nrec, d_in, d_out, d_ad,
@@ -193,7 +187,7 @@ int cs_sessions(bool decrypt, noise_gpu_cs *cs, const uint32_t *d_sess, const ui
                                    len, d_status, nrec);
   if (rc || nrec == 0) return rc;
   const hipStream_t st = (hipStream_t)stream;
-  CS_TRY(cs_scratch(cs, cs_scratch_layout(false, false, nrec).total, st));
+  API_TRY(cs_scratch(cs, cs_scratch_layout(false, false, nrec).total, st));
   return cs_done(cs_inorder_call(
       decrypt, cs->t, cs_columns(d_sess, nullptr), nrec, cs->scratch, d_status, st, [&](const CsColumns &mine) {
         return launch_aead_sessions(decrypt, cs->t.keys, cs->t.nsess, reinterpret_cast<const uint32_t *>(mine.sess),
@@ -245,9 +239,9 @@ int noise_gpu_cs_set(noise_gpu_cs *cs, uint64_t first, uint64_t count, const uin
   if (rc || count == 0) return rc;
   if (!d_keys && !d_n) return api_arg_fail("neither key rows nor counters given");
   if ((rc = api_check_device())) return rc;
-  CS_TRY(launch_cs_set(cs->t, first, count, d_keys, key_stride, d_n, (hipStream_t)stream));
+  API_TRY(launch_cs_set(cs->t, first, count, d_keys, key_stride, d_n, (hipStream_t)stream));
   // a new key starts a new nonce space
-  if (d_keys && cs->w.next) CS_TRY(cs_window_clear(cs, first, count, (hipStream_t)stream));
+  if (d_keys && cs->w.next) API_TRY(cs_window_clear(cs, first, count, (hipStream_t)stream));
   return NOISE_GPU_OK;
 }
 
@@ -258,8 +252,8 @@ int noise_gpu_cs_get(const noise_gpu_cs *cs, uint64_t first, uint64_t count, uin
   if ((rc = api_check_device())) return rc;
   const hipStream_t st = (hipStream_t)stream;
   if (d_keys)
-    CS_TRY(hipMemcpyAsync(d_keys, cs->t.keys + 32 * first, 32 * count, hipMemcpyDeviceToDevice, st));
-  if (d_n) CS_TRY(hipMemcpyAsync(d_n, cs->t.ctr + first, 8 * count, hipMemcpyDeviceToDevice, st));
+    API_TRY(hipMemcpyAsync(d_keys, cs->t.keys + 32 * first, 32 * count, hipMemcpyDeviceToDevice, st));
+  if (d_n) API_TRY(hipMemcpyAsync(d_n, cs->t.ctr + first, 8 * count, hipMemcpyDeviceToDevice, st));
   return NOISE_GPU_OK;
 }
 
@@ -270,7 +264,7 @@ int noise_gpu_cs_rekey(noise_gpu_cs *cs, const uint32_t *d_sess, uint64_t count,
   if (count == 0) return NOISE_GPU_OK;
   int rc = api_check_device();
   if (rc) return rc;
-  CS_TRY(launch_cs_rekey(cs->t, d_sess, count, (hipStream_t)stream));
+  API_TRY(launch_cs_rekey(cs->t, d_sess, count, (hipStream_t)stream));
   return NOISE_GPU_OK;
 }
 
@@ -281,9 +275,9 @@ int noise_gpu_cs_assign(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t sess_s
   if (rc || nrec == 0) return rc;
   if ((rc = api_check_device())) return rc;
   const hipStream_t st = (hipStream_t)stream;
-  CS_TRY(cs_scratch(cs, cs_assign_scratch_bytes(nrec), st));
+  API_TRY(cs_scratch(cs, cs_assign_scratch_bytes(nrec), st));
   const CsAssign a{d_sess, sess_stride, d_nonce, nonce_stride, nullptr, 0, nullptr, 0, d_status, nrec};
-  CS_TRY(launch_cs_assign(cs->t, a, cs->scratch, st));
+  API_TRY(launch_cs_assign(cs->t, a, cs->scratch, st));
   return NOISE_GPU_OK;
 }
 
@@ -317,8 +311,8 @@ int noise_gpu_cswin_reset(noise_gpu_cs *cs, uint64_t first, uint64_t count, void
   if ((rc = api_check_device())) return rc;
   const hipStream_t st = (hipStream_t)stream;
   const bool fresh = !cs->w.next;
-  CS_TRY(cs_window_rows(cs, st));
-  if (!fresh) CS_TRY(cs_window_clear(cs, first, count, st));
+  API_TRY(cs_window_rows(cs, st));
+  if (!fresh) API_TRY(cs_window_clear(cs, first, count, st));
   return NOISE_GPU_OK;
 }
 
@@ -330,14 +324,14 @@ int noise_gpu_cswin_get(const noise_gpu_cs *cs, uint64_t first, uint64_t count, 
   if ((rc = api_check_device())) return rc;
   const hipStream_t st = (hipStream_t)stream;
   if (!cs->w.next) {  // never used a window: the fresh state
-    if (d_next) CS_TRY(hipMemsetAsync(d_next, 0, 8 * count, st));
-    if (d_bits) CS_TRY(hipMemsetAsync(d_bits, 0, kCsWinRow * count, st));
+    if (d_next) API_TRY(hipMemsetAsync(d_next, 0, 8 * count, st));
+    if (d_bits) API_TRY(hipMemsetAsync(d_bits, 0, kCsWinRow * count, st));
     return NOISE_GPU_OK;
   }
   if (d_next)
-    CS_TRY(hipMemcpyAsync(d_next, cs->w.next + first, 8 * count, hipMemcpyDeviceToDevice, st));
+    API_TRY(hipMemcpyAsync(d_next, cs->w.next + first, 8 * count, hipMemcpyDeviceToDevice, st));
   if (d_bits)
-    CS_TRY(hipMemcpyAsync(d_bits, reinterpret_cast<const uint8_t *>(cs->w.bits) + kCsWinRow * first,
+    API_TRY(hipMemcpyAsync(d_bits, reinterpret_cast<const uint8_t *>(cs->w.bits) + kCsWinRow * first,
                           kCsWinRow * count, hipMemcpyDeviceToDevice, st));
   return NOISE_GPU_OK;
 }
@@ -350,9 +344,9 @@ int noise_gpu_cswin_filter(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t ses
   if (!d_status) return api_arg_fail("null status buffer");
   if ((rc = api_check_device())) return rc;
   const hipStream_t st = (hipStream_t)stream;
-  CS_TRY(cs_window_rows(cs, st));
+  API_TRY(cs_window_rows(cs, st));
   const CwBatch b{d_sess, sess_stride, d_nonce, nonce_stride, nrec};
-  CS_TRY(launch_cw_filter(cs->t, cs->w, b, d_status, nullptr, 0, st));
+  API_TRY(launch_cw_filter(cs->t, cs->w, b, d_status, nullptr, 0, st));
   return NOISE_GPU_OK;
 }
 
@@ -364,10 +358,10 @@ int noise_gpu_cswin_commit(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t ses
   if (!d_status) return api_arg_fail("null status buffer");
   if ((rc = api_check_device())) return rc;
   const hipStream_t st = (hipStream_t)stream;
-  CS_TRY(cs_window_rows(cs, st));
-  CS_TRY(cs_scratch(cs, cw_commit_scratch_bytes(nrec), st));
+  API_TRY(cs_window_rows(cs, st));
+  API_TRY(cs_scratch(cs, cw_commit_scratch_bytes(nrec), st));
   const CwBatch b{d_sess, sess_stride, d_nonce, nonce_stride, nrec};
-  CS_TRY(launch_cw_commit(cs->t, cs->w, b, d_status, cs->scratch, st));
+  API_TRY(launch_cw_commit(cs->t, cs->w, b, d_status, cs->scratch, st));
   return NOISE_GPU_OK;
 }
 
@@ -377,8 +371,8 @@ int noise_gpu_cswin_decrypt_records(noise_gpu_cs *cs, const noise_gpu_record *d_
   const int rc = cs_check_records(cs, true, d_recs, nrec, d_in, d_out, d_status);
   if (rc || nrec == 0) return rc;
   const hipStream_t st = (hipStream_t)stream;
-  CS_TRY(cs_window_rows(cs, st));
-  CS_TRY(cs_scratch(cs, cs_scratch_layout(true, true, nrec).total, st));
+  API_TRY(cs_window_rows(cs, st));
+  API_TRY(cs_scratch(cs, cs_scratch_layout(true, true, nrec).total, st));
   return cs_done(cs_window_call(
       cs->t, cs->w, cs_columns(d_recs), nrec, cs->scratch, d_out, 0, 0, d_status, st, [&](const CsColumns &mine) {
         return launch_aead_records(true, cs->t.keys, cs->t.nsess, mine.recs, nrec, d_in, d_out, d_ad, d_status, st,
@@ -394,8 +388,8 @@ int noise_gpu_cswin_decrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess,
                                    d_status, nrec);
   if (rc || nrec == 0) return rc;
   const hipStream_t st = (hipStream_t)stream;
-  CS_TRY(cs_window_rows(cs, st));
-  CS_TRY(cs_scratch(cs, cs_scratch_layout(true, false, nrec).total, st));
+  API_TRY(cs_window_rows(cs, st));
+  API_TRY(cs_scratch(cs, cs_scratch_layout(true, false, nrec).total, st));
   return cs_done(cs_window_call(
       cs->t, cs->w, cs_columns(d_sess, d_nonces), nrec, cs->scratch, d_out, out_stride, len, d_status, st,
       [&](const CsColumns &mine) {

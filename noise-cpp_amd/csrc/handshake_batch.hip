@@ -41,12 +41,6 @@ struct noise_gpu_hs {
 
 namespace {
 
-#define HS_TRY(expr)                                          \
-  do {                                                        \
-    hipError_t e_ = (expr);                                   \
-    if (e_ != hipSuccess) return api_hip_fail(e_, #expr);     \
-  } while (0)
-
 bool my_turn(const noise_gpu_hs *hs) {
   if (hs->prog.one_way) return hs->initiator;
   return ((hs->msg % 2) == 0) == hs->initiator;
@@ -195,8 +189,8 @@ int noise_gpu_hs_set_key(noise_gpu_hs *hs, int which, const uint8_t *d_keys, uin
   HsWords8 none{};
   // stride 0: one key for every session -- install (and derive) it in row 0
   // only, then copy the row-0 slots to the others
-  HS_TRY(launch_hs_set_key(hs->S, stride ? hs->n : 1, slot, d_keys, stride, none, 0, derive, st));
-  if (!stride) HS_TRY(launch_hs_bcast_key(hs->S, hs->n, slot, derive ? 2 : 1, st));
+  API_TRY(launch_hs_set_key(hs->S, stride ? hs->n : 1, slot, d_keys, stride, none, 0, derive, st));
+  if (!stride) API_TRY(launch_hs_bcast_key(hs->S, hs->n, slot, derive ? 2 : 1, st));
   hs->has[slot] = true;
   if (derive) hs->has[slot + 1] = true;
   return NOISE_GPU_OK;
@@ -206,7 +200,7 @@ int noise_gpu_hs_set_psks(noise_gpu_hs *hs, const uint8_t *d_psks, void *stream)
   if (!hs || !d_psks) return api_arg_fail("null batch / psks");
   if (hs->started) return api_arg_fail("psks are set before noise_gpu_hs_start");
   if (!hs->prog.npsk) return api_arg_fail("the pattern has no psk modifier");
-  HS_TRY(hipMemcpyAsync(hs->psks, d_psks, hs->n * hs->prog.npsk * 32, hipMemcpyDeviceToDevice,
+  API_TRY(hipMemcpyAsync(hs->psks, d_psks, hs->n * hs->prog.npsk * 32, hipMemcpyDeviceToDevice,
                         (hipStream_t)stream));
   hs->psks_set = true;
   return NOISE_GPU_OK;
@@ -227,7 +221,7 @@ int noise_gpu_hs_start(noise_gpu_hs *hs, const noise_gpu_span *prologue, void *s
         noise::crypto::blake2b(reinterpret_cast<const uint8_t *>(name.data()), name.size());
     std::memcpy(h0.w, d.data(), 64);
   }
-  HS_TRY(launch_hs_init(hs->S, hs->n, h0, span_of(prologue), st));
+  API_TRY(launch_hs_init(hs->S, hs->n, h0, span_of(prologue), st));
   // pre-messages: the initiator's keys first, then the responder's
   for (int side = 0; side < 2; ++side) {
     const bool mine = (side == 0) == hs->initiator;
@@ -238,7 +232,7 @@ int noise_gpu_hs_start(noise_gpu_hs *hs, const noise_gpu_span *prologue, void *s
       else return api_arg_fail("bad pre-message token");
       if (!hs->has[slot]) return api_arg_fail("pre-message key missing (noise_gpu_hs_set_key)");
       const bool key = t == PatternToken::E && hs->prog.psk_mode;
-      HS_TRY(launch_hs_key_token(hs->S, hs->n, slot, 0, HsSpan{}, true, key, st));
+      API_TRY(launch_hs_key_token(hs->S, hs->n, slot, 0, HsSpan{}, true, key, st));
       if (key) {
         hs->has_k = true;
         hs->nonce = 0;
@@ -264,7 +258,7 @@ int noise_gpu_hs_write_message(noise_gpu_hs *hs, const noise_gpu_span *payload,
   const uint32_t need = overhead(hs);
   if (payload && !payload->len && (uint64_t)payload->len_all + need > 65535)
     return api_arg_fail("message (payload + overhead) exceeds 65535 bytes");
-  if (payload && payload->len) HS_TRY(launch_hs_check_len(hs->S, n, payload->len, need, need, st));
+  if (payload && payload->len) API_TRY(launch_hs_check_len(hs->S, n, payload->len, need, need, st));
   HsSpan m = span_of(msg);
   m.len = nullptr;
   for (PatternToken t : hs->prog.msgs[hs->msg]) {
@@ -275,10 +269,10 @@ int noise_gpu_hs_write_message(noise_gpu_hs *hs, const noise_gpu_span *payload,
           const hipError_t e =
               launch_hs_set_key(hs->S, n, kHsEsk, nullptr, 0, seed, hs->drbg_ctr++, true, st);
           wipe_words(seed);
-          HS_TRY(e);
+          API_TRY(e);
           hs->has[kHsEsk] = hs->has[kHsEpk] = true;
         }
-        HS_TRY(launch_hs_key_token(hs->S, n, kHsEpk, 1, m, true, hs->prog.psk_mode, st));
+        API_TRY(launch_hs_key_token(hs->S, n, kHsEpk, 1, m, true, hs->prog.psk_mode, st));
         m.add += 32;
         if (hs->prog.psk_mode) {
           hs->has_k = true;
@@ -288,14 +282,14 @@ int noise_gpu_hs_write_message(noise_gpu_hs *hs, const noise_gpu_span *payload,
       }
       case PatternToken::S: {
         if (!hs->has[kHsSpk]) return api_arg_fail("static key missing");
-        HS_TRY(launch_hs_encrypt_hash(hs->S, n, hs->has_k, hs->nonce, kHsSpk, HsSpan{}, m,
+        API_TRY(launch_hs_encrypt_hash(hs->S, n, hs->has_k, hs->nonce, kHsSpk, HsSpan{}, m,
                                       nullptr, st));
         m.add += hs->has_k ? 48 : 32;
         if (hs->has_k) ++hs->nonce;
         break;
       }
       case PatternToken::Psk: {
-        HS_TRY(launch_hs_psk(hs->S, n, hs->psks, (uint32_t)hs->prog.npsk,
+        API_TRY(launch_hs_psk(hs->S, n, hs->psks, (uint32_t)hs->prog.npsk,
                              (uint32_t)hs->psk_next++, st));
         hs->has_k = true;
         hs->nonce = 0;
@@ -304,7 +298,7 @@ int noise_gpu_hs_write_message(noise_gpu_hs *hs, const noise_gpu_span *payload,
       default: {
         int sk, pk;
         if (!dh_slots(hs, t, sk, pk)) return api_arg_fail("DH with a missing key");
-        HS_TRY(launch_hs_dh(hs->S, n, sk, pk, st));
+        API_TRY(launch_hs_dh(hs->S, n, sk, pk, st));
         hs->has_k = true;
         hs->nonce = 0;
       }
@@ -312,7 +306,7 @@ int noise_gpu_hs_write_message(noise_gpu_hs *hs, const noise_gpu_span *payload,
   }
   HsSpan p = span_of(payload);
   if (!payload) p.base = m.base;  // empty payloads: len 0, never dereferenced
-  HS_TRY(launch_hs_encrypt_hash(hs->S, n, hs->has_k, hs->nonce, -1, p, m, d_msg_len, st));
+  API_TRY(launch_hs_encrypt_hash(hs->S, n, hs->has_k, hs->nonce, -1, p, m, d_msg_len, st));
   if (hs->has_k) ++hs->nonce;
   ++hs->msg;
   return NOISE_GPU_OK;
@@ -329,7 +323,7 @@ int noise_gpu_hs_read_message(noise_gpu_hs *hs, const noise_gpu_span *msg,
   const uint64_t n = hs->n;
   const uint32_t need = overhead(hs);
   if (msg->len) {
-    HS_TRY(launch_hs_check_len(hs->S, n, msg->len, need, 0, st));
+    API_TRY(launch_hs_check_len(hs->S, n, msg->len, need, 0, st));
   } else if (msg->len_all < need || msg->len_all > 65535) {
     return api_arg_fail("message length outside [overhead, 65535]");
   }
@@ -339,7 +333,7 @@ int noise_gpu_hs_read_message(noise_gpu_hs *hs, const noise_gpu_span *msg,
   for (PatternToken t : hs->prog.msgs[hs->msg]) {
     switch (t) {
       case PatternToken::E: {
-        HS_TRY(launch_hs_key_token(hs->S, n, kHsRe, 2, m, true, hs->prog.psk_mode, st));
+        API_TRY(launch_hs_key_token(hs->S, n, kHsRe, 2, m, true, hs->prog.psk_mode, st));
         hs->has[kHsRe] = true;
         m.add += 32;
         if (hs->prog.psk_mode) {
@@ -352,7 +346,7 @@ int noise_gpu_hs_read_message(noise_gpu_hs *hs, const noise_gpu_span *msg,
         HsSpan c = m;
         c.len = nullptr;
         c.len_u = hs->has_k ? 48 : 32;
-        HS_TRY(launch_hs_decrypt_hash(hs->S, n, hs->has_k, hs->nonce, c, kHsRs, HsSpan{}, nullptr,
+        API_TRY(launch_hs_decrypt_hash(hs->S, n, hs->has_k, hs->nonce, c, kHsRs, HsSpan{}, nullptr,
                                       st));
         hs->has[kHsRs] = true;
         m.add += c.len_u;
@@ -360,7 +354,7 @@ int noise_gpu_hs_read_message(noise_gpu_hs *hs, const noise_gpu_span *msg,
         break;
       }
       case PatternToken::Psk: {
-        HS_TRY(launch_hs_psk(hs->S, n, hs->psks, (uint32_t)hs->prog.npsk,
+        API_TRY(launch_hs_psk(hs->S, n, hs->psks, (uint32_t)hs->prog.npsk,
                              (uint32_t)hs->psk_next++, st));
         hs->has_k = true;
         hs->nonce = 0;
@@ -369,7 +363,7 @@ int noise_gpu_hs_read_message(noise_gpu_hs *hs, const noise_gpu_span *msg,
       default: {
         int sk, pk;
         if (!dh_slots(hs, t, sk, pk)) return api_arg_fail("DH with a missing key");
-        HS_TRY(launch_hs_dh(hs->S, n, sk, pk, st));
+        API_TRY(launch_hs_dh(hs->S, n, sk, pk, st));
         hs->has_k = true;
         hs->nonce = 0;
       }
@@ -381,16 +375,16 @@ int noise_gpu_hs_read_message(noise_gpu_hs *hs, const noise_gpu_span *msg,
   else c.len_u = msg->len_all - c.add;
   HsSpan p = span_of(payload);
   if (!payload) p.base = m.base;  // empty payloads: nothing is written
-  HS_TRY(launch_hs_decrypt_hash(hs->S, n, hs->has_k, hs->nonce, c, -1, p, d_payload_len, st));
+  API_TRY(launch_hs_decrypt_hash(hs->S, n, hs->has_k, hs->nonce, c, -1, p, d_payload_len, st));
   if (hs->has_k) ++hs->nonce;
   ++hs->msg;
-  if (d_status) HS_TRY(launch_hs_status(hs->S, n, d_status, st));
+  if (d_status) API_TRY(launch_hs_status(hs->S, n, d_status, st));
   return NOISE_GPU_OK;
 }
 
 int noise_gpu_hs_status(const noise_gpu_hs *hs, uint8_t *d_status, void *stream) {
   if (!hs || !d_status) return api_arg_fail("null batch / status");
-  HS_TRY(launch_hs_status(hs->S, hs->n, d_status, (hipStream_t)stream));
+  API_TRY(launch_hs_status(hs->S, hs->n, d_status, (hipStream_t)stream));
   return NOISE_GPU_OK;
 }
 
@@ -402,7 +396,7 @@ int noise_gpu_hs_split(noise_gpu_hs *hs, uint8_t *d_k1, uint8_t *d_k2, uint8_t *
         reinterpret_cast<uintptr_t>(d_hash) | reinterpret_cast<uintptr_t>(d_rs)) & 15u) != 0)
     return api_arg_fail("split outputs must be 16-byte aligned");
   if (d_rs && !hs->has[kHsRs]) return api_arg_fail("no remote static key in this pattern");
-  HS_TRY(launch_hs_split(hs->S, hs->n, d_k1, d_k2, d_hash, d_rs, (hipStream_t)stream));
+  API_TRY(launch_hs_split(hs->S, hs->n, d_k1, d_k2, d_hash, d_rs, (hipStream_t)stream));
   return NOISE_GPU_OK;
 }
 

@@ -1,6 +1,7 @@
 // launchers.hpp -- internal interface between the C-ABI translation units
-// (noise_gpu_api.hip, cstate_api.hip, handshake_batch.hip) and the kernels'
-// launchers, and the helpers those translation units share.
+// (noise_gpu_api.hip with host_ctx.hip, cstate_api.hip, handshake_batch.hip)
+// and the kernels' launchers, and the helpers those translation units share
+// (api_*, API_TRY).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -274,10 +275,18 @@ hipError_t launch_cw_finish(const uint8_t *pre, uint8_t *status, const noise_gpu
                             uint8_t *out, uint64_t out_stride, uint32_t len, uint64_t nrec,
                             hipStream_t stream);
 
-// C-ABI helpers shared by the API translation units (defined in noise_gpu_api.hip)
-int api_hip_fail(hipError_t e, const char *what);
-int api_arg_fail(const char *msg);
-int api_check_device();
+// C-ABI helpers shared by the API translation units (defined in noise_gpu_api.hip).
+// A failure sets the thread's noise_gpu_last_error() text and returns its status
+int api_fail(int status, const char *msg);
+int api_arg_fail(const char *msg);                 // NOISE_GPU_E_ARG
+int api_hip_fail(hipError_t e, const char *what);  // NOISE_GPU_E_HIP, "what: <HIP's error text>"
+// a HIP call that must succeed, reported under its own text
+#define API_TRY(expr)                                                      \
+  do {                                                                     \
+    hipError_t e_ = (expr);                                                \
+    if (e_ != hipSuccess) return ::noise_amd::api_hip_fail(e_, #expr);     \
+  } while (0)
+int api_check_device();  // is a gfx950 device current?
 // a uniform batch's buffers and strides.  enc: in = len-byte records, out = len+16
 int api_check_uniform(bool decrypt, const void *in, uint64_t in_stride, const void *out,
                       uint64_t out_stride, uint32_t len, const void *ad, uint32_t ad_len,

@@ -6,7 +6,7 @@
 //     so they share it;
 //   - the companion set of the records DAG (AuxStream), created on first use.
 // records_scratch_release drops the record; a stream the engine created is
-// closed through it (noise_gpu_api.hip, OwnedStream), a caller's stream by
+// closed through it (host_ctx.hpp, OwnedStream), a caller's stream by
 // noise_gpu_scratch_release.
 #pragma once
 #include <hip/hip_runtime.h>

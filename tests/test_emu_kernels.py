@@ -180,7 +180,7 @@ def test_host_entry_points_emulated_and_wiped(emu):
 
 
 def test_resident_wait_is_bounded_emulated(emu):
-    """OneCtx::wait (noise_gpu_api.hip) returns NOISE_GPU_E_HIP for a request
+    """OneCtx::wait (host_ctx.hip) returns NOISE_GPU_E_HIP for a request
     line the resident instance never takes (its check word corrupted by an
     emulation-only hook): with instances that leave at once (relaunch cap)
     and with one long-lived instance that keeps polling (the 10-s limit,

@@ -1,4 +1,5 @@
-// emu_api.cpp -- the C ABI's host-buffer entry points (noise_gpu_api.hip)
+// emu_api.cpp -- the C ABI's host-buffer entry points (noise_gpu_api.hip,
+// host_ctx.hip)
 // with their kernels (the latency kernel single_kernels.hip, the lane walk,
 // the records path, the host pipeline) compiled as host C++ through the HIP
 // stand-in, under AddressSanitizer, against the C oracle.  After every call
@@ -32,7 +33,7 @@
 
 namespace noise_amd {  // single_kernels.hip: emulated asynchronously (below)
 void k_aead_resident(uint8_t *req, uint8_t *base, uint32_t last, uint64_t idle_ticks);
-extern uint32_t emu_req_check_flip;  // noise_gpu_api.hip (emulation build only)
+extern uint32_t emu_req_check_flip;  // host_ctx.hip (emulation build only)
 }
 
 extern "C" {
@@ -190,6 +191,122 @@ static void unaligned_uniform(noise_gpu_ctx *ctx, const uint8_t key[32], uint64_
   CHECK(rc == NOISE_GPU_OK && back == pt, "%s: unaligned decrypt_uniform_host rc=%d", what, rc);
   for (uint32_t i = 0; i < R; ++i) CHECK(st[i] == 0, "%s: unaligned uniform_host status %u", what, i);
   scan("unaligned decrypt_uniform_host", resident);
+}
+
+// One thread on more devices than it has context slots: devices 0 and 16
+// share slot 0 (device % 16), so each hipSetDevice between them makes the
+// staging, latency and pipeline contexts drop what they hold on the old
+// device and bind to the new one.  Every host-buffer path once per device,
+// against the oracle, every allocation zero after each call.
+static void one_device_round(int dev, const uint8_t key[32], std::mt19937_64 &rng, bool resident) {
+  CHECK(hipSetDevice(dev) == hipSuccess, "hipSetDevice(%d)", dev);
+  auto rbytes = [&](size_t n) {
+    std::vector<uint8_t> v(n);
+    for (auto &x : v) x = (uint8_t)rng();
+    return v;
+  };
+  // the latency kernel (64 bytes, 16 of AD) and the copy-staged path (65536
+  // bytes: the first size past the latency kernel)
+  for (size_t L : {64ul, 65536ul}) {
+    const uint64_t n = rng() % 1000;
+    const auto pt = rbytes(L), ad = rbytes(16);
+    std::vector<uint8_t> want(L + 16), buf(pt);
+    buf.resize(L + 16);
+    oracle_noise_encrypt(key, n, ad.data(), 16, pt.data(), L, want.data());
+    ++calls;
+    int rc = noise_gpu_encrypt_host(key, n, ad.data(), 16, buf.data(), L);
+    CHECK(rc == NOISE_GPU_OK && buf == want, "device %d: encrypt_host L=%zu rc=%d", dev, L, rc);
+    scan("shared slot encrypt_host", resident);
+    ++calls;
+    rc = noise_gpu_decrypt_host(key, n, ad.data(), 16, buf.data(), L + 16);
+    CHECK(rc == NOISE_GPU_OK && std::memcmp(buf.data(), pt.data(), L) == 0,
+          "device %d: decrypt_host L=%zu rc=%d", dev, L, rc);
+    scan("shared slot decrypt_host", resident);
+  }
+  if (resident) return;  // the mode is the latency context's alone
+  {  // a descriptor batch of 2 records
+    const uint32_t L[2] = {100, 700};
+    const auto pt = rbytes(1536);
+    std::vector<noise_gpu_record> enc(2), dec(2);
+    for (uint32_t i = 0; i < 2; ++i) {
+      enc[i] = noise_gpu_record{512ull * i, 1024ull * i, 40 + i, 0, L[i], 0, 0, 0};
+      dec[i] = noise_gpu_record{1024ull * i, 512ull * i, 40 + i, 0, L[i], 0, 0, 0};
+    }
+    std::vector<uint8_t> ct(2048), back(1536), st(2, 9), w(1024);
+    ++calls;
+    int rc = noise_gpu_encrypt_records_host(key, 1, enc.data(), 2, pt.data(), pt.size(), ct.data(),
+                                            ct.size(), nullptr, 0);
+    CHECK(rc == NOISE_GPU_OK, "device %d: encrypt_records_host rc=%d", dev, rc);
+    for (uint32_t i = 0; i < 2; ++i) {
+      oracle_noise_encrypt(key, 40 + i, nullptr, 0, pt.data() + 512 * i, L[i], w.data());
+      CHECK(std::memcmp(ct.data() + 1024 * i, w.data(), L[i] + 16) == 0,
+            "device %d: records_host record %u", dev, i);
+    }
+    scan("shared slot encrypt_records_host");
+    ++calls;
+    rc = noise_gpu_decrypt_records_host(key, 1, dec.data(), 2, ct.data(), ct.size(), back.data(),
+                                        back.size(), nullptr, 0, st.data());
+    CHECK(rc == NOISE_GPU_OK, "device %d: decrypt_records_host rc=%d", dev, rc);
+    for (uint32_t i = 0; i < 2; ++i)
+      CHECK(st[i] == 0 && std::memcmp(back.data() + 512 * i, pt.data() + 512 * i, L[i]) == 0,
+            "device %d: records_host decrypted record %u", dev, i);
+    scan("shared slot decrypt_records_host");
+  }
+  {  // a uniform batch of 3 records of 64 bytes through the pipeline
+    const uint32_t L = 64, R = 3;
+    const auto pt = rbytes((size_t)L * R);
+    std::vector<uint8_t> ct((size_t)(L + 16) * R), back((size_t)L * R), st(R, 9), w(L + 16);
+    double secs = 0;
+    ++calls;
+    int rc = noise_gpu_encrypt_uniform_host(key, 21, pt.data(), L, ct.data(), L + 16, L, R, &secs);
+    CHECK(rc == NOISE_GPU_OK, "device %d: encrypt_uniform_host rc=%d", dev, rc);
+    for (uint32_t i = 0; i < R; ++i) {
+      oracle_noise_encrypt(key, 21 + i, nullptr, 0, pt.data() + (size_t)i * L, L, w.data());
+      CHECK(std::memcmp(ct.data() + (size_t)i * (L + 16), w.data(), L + 16) == 0,
+            "device %d: uniform_host record %u", dev, i);
+    }
+    scan("shared slot encrypt_uniform_host");
+    ++calls;
+    rc = noise_gpu_decrypt_uniform_host(key, 21, ct.data(), L + 16, back.data(), L, L, st.data(), R,
+                                        &secs);
+    CHECK(rc == NOISE_GPU_OK && back == pt, "device %d: decrypt_uniform_host rc=%d", dev, rc);
+    for (uint32_t i = 0; i < R; ++i) CHECK(st[i] == 0, "device %d: uniform_host status %u", dev, i);
+    scan("shared slot decrypt_uniform_host");
+  }
+}
+
+static void shared_slot_devices(const uint8_t key[32], std::mt19937_64 &rng) {
+  enter("devices 0 and 16 in one context slot");
+  emu::device_count = 17;
+  for (int dev : {0, 16, 0}) one_device_round(dev, key, rng, false);
+  // resident mode across the switch: the instance of device 0 (synchronous
+  // here: it has idled out) is stopped by the re-target, and the context,
+  // still resident, launches its next one on device 16
+  CHECK(noise_gpu_set_resident(1, 300) == NOISE_GPU_OK, "shared slot: set_resident on");
+  for (int dev : {0, 16}) one_device_round(dev, key, rng, true);
+  CHECK(noise_gpu_set_resident(0, 0) == NOISE_GPU_OK, "shared slot: set_resident off");
+  CHECK(noise_gpu_thread_release() == NOISE_GPU_OK, "shared slot: thread_release");
+  CHECK(emu::allocations().empty(), "shared slot: thread_release left %zu allocations",
+        emu::allocations().size());
+  CHECK(hipSetDevice(0) == hipSuccess, "hipSetDevice(0)");
+  emu::device_count = 1;
+  // an explicit context's calls allocate in the context, not in the thread's
+  // own: what one call left allocated survives noise_gpu_thread_release and
+  // goes with noise_gpu_ctx_destroy
+  noise_gpu_ctx *ctx = nullptr;
+  CHECK(noise_gpu_ctx_create(0, &ctx) == NOISE_GPU_OK && ctx, "own contexts: ctx_create");
+  std::vector<uint8_t> buf(64 + 16, 0x5a), want(64 + 16);
+  oracle_noise_encrypt(key, 1, nullptr, 0, buf.data(), 64, want.data());
+  ++calls;
+  const int rc = noise_gpu_ctx_encrypt_host(ctx, key, 1, nullptr, 0, buf.data(), 64);
+  CHECK(rc == NOISE_GPU_OK && buf == want, "own contexts: ctx encrypt_host rc=%d", rc);
+  scan("own contexts: ctx encrypt_host");
+  const size_t live = emu::allocations().size();
+  CHECK(noise_gpu_thread_release() == NOISE_GPU_OK && live > 0 && emu::allocations().size() == live,
+        "own contexts: %zu allocations before thread_release, %zu after", live,
+        emu::allocations().size());
+  CHECK(noise_gpu_ctx_destroy(ctx) == NOISE_GPU_OK && emu::allocations().empty(),
+        "own contexts: ctx_destroy left %zu allocations", emu::allocations().size());
 }
 
 int main() {
@@ -490,6 +607,7 @@ int main() {
     CHECK(emu::allocations().size() == live0, "thread exit left %zu allocations",
           emu::allocations().size() - live0);
   }
+  shared_slot_devices(key, rng);
   // every per-thread context released: nothing the engine allocated is left
   CHECK(noise_gpu_thread_release() == NOISE_GPU_OK, "thread_release");
   CHECK(emu::allocations().empty(), "thread_release left %zu allocations", emu::allocations().size());

@@ -94,6 +94,11 @@ inline std::vector<std::thread> async_threads;
 // the data and its byte count: a test can watch what lands where
 inline void (*store_hook)(const void *dst, const void *data, int n) = nullptr;
 
+// The emulated devices, all gfx950: one unless a test program raises the
+// count; each host thread has its own current device (hipSetDevice), 0 at first.
+inline int device_count = 1;
+inline thread_local int device = 0;
+
 // every hipMalloc / hipHostMalloc allocation, for tests that inspect what
 // the engine leaves in its buffers (secret hygiene)
 struct Alloc {
@@ -342,7 +347,7 @@ inline hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) {  // n
 }
 inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
 inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-inline hipError_t hipGetDevice(int *d) { *d = 0; return hipSuccess; }
+inline hipError_t hipGetDevice(int *d) { *d = emu::device; return hipSuccess; }
 inline hipError_t hipMalloc(void **p, size_t n) {
   *p = emu::track(std::calloc(n ? n : 1, 1), n, false);
   return *p ? hipSuccess : hipErrorMemoryAllocation;
@@ -421,8 +426,12 @@ inline hipError_t hipStreamSynchronize(hipStream_t) {
 inline hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
 inline hipError_t hipEventDestroy(hipEvent_t) { return hipSuccess; }
 inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
-inline hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
-inline hipError_t hipSetDevice(int d) { return d == 0 ? hipSuccess : hipErrorInvalidDevice; }
+inline hipError_t hipGetDeviceCount(int *n) { *n = emu::device_count; return hipSuccess; }
+inline hipError_t hipSetDevice(int d) {
+  if (d < 0 || d >= emu::device_count) return hipErrorInvalidDevice;
+  emu::device = d;
+  return hipSuccess;
+}
 struct hipDeviceProp_t {
   char gcnArchName[256];
 };
