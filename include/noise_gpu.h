@@ -512,6 +512,88 @@ int noise_gpu_cswin_decrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess,
                                      uint64_t in_stride, uint8_t *d_out, uint64_t out_stride,
                                      uint32_t len, uint8_t *d_status, uint64_t nrec, void *stream);
 
+/* ---- datagram wire format on a table: seal and open ------------------------
+ * What a datagram endpoint over the tables still lacked: the wire.  One packet
+ * is a 16-byte header, then ct || tag:
+ *   bytes 0..3    LE32 type      a constant the caller passes to both calls
+ *   bytes 4..7    LE32 receiver  the session's index in the RECEIVER's table
+ *   bytes 8..15   LE64 counter   the Noise nonce n
+ *   bytes 16..    ct || tag      len + 16 bytes, ChaChaPoly, nonce 0^32 ||
+ *                                LE64(counter), no AD
+ * so a packet is 32 + len bytes, 0 <= len <= NOISE_GPU_DGRAM_MAX_LEN.  With
+ * type = 4 this is, byte for byte, a WireGuard transport data message.  The
+ * header is 16 bytes on purpose: a packet slot at a 16-byte aligned address
+ * has its ciphertext 16-byte aligned too, so its record takes the tile
+ * classes of the records kernels and not the generic lane walk.  Unaligned
+ * slots work and take the generic path.  The header is not authenticated as
+ * AD (as in the reference's transport records and in WireGuard): a changed
+ * counter or receiver fails the tag or names a keyless / out-of-range row, a
+ * changed type is refused as malformed.
+ *
+ * Spans are those of the batched handshakes: record i's bytes start at base +
+ * (off ? off[i] : i * stride) and are len ? len[i] : len_all long.  len_sum is
+ * the hint of the _sized calls (the sum of the payload lengths, 0 = unknown).
+ * Both calls are asynchronous on `stream`, never synchronise with the host,
+ * obey the table's one-stream-at-a-time contract and use the table's scratch
+ * only; d_recs (nrec descriptors, 8-byte aligned) is the caller's.
+ *
+ * seal does, stream-ordered, what this sequence does:
+ *   1. recs[i] = {in_off = payload offset, out_off = packet offset + 16, len,
+ *      key_idx = d_sess[i]}
+ *   2. noise_gpu_cs_encrypt_records(cs, recs, .., d_in = payload->base,
+ *      d_out = pkt->base, ..)
+ *   3. for every REC_OK record the header {type, d_peer ? d_peer[sess] : sess,
+ *      recs[i].nonce} at the packet offset.
+ * A payload longer than NOISE_GPU_DGRAM_MAX_LEN gets REC_MALFORMED and takes
+ * no nonce: its neighbours' nonces are consecutive.  REC_BAD_KEY / REC_NONCE
+ * as in assignment.  For a status other than REC_OK nothing at all is written
+ * to the packet slot and d_pkt_len[i] = 0; otherwise d_pkt_len[i] = 32 + len.
+ * In place (the plaintext already at packet offset + 16) is allowed.  The
+ * counters end where noise_gpu_cs_encrypt_records leaves them.
+ *
+ * open gives every packet the status, output bytes and window state of the
+ * windowed loop above, run over the well-formed packets in record order with
+ * key_idx = receiver, nonce = counter, in_off = packet offset + 16, len =
+ * packet length - 32.  A packet is malformed if it is shorter than 32 bytes,
+ * longer than 32 + NOISE_GPU_DGRAM_MAX_LEN, or of another type.  Malformed
+ * packets are taken out before the loop: REC_MALFORMED, never read past the
+ * header (not read at all below 32 bytes), nothing written, no table memory
+ * touched, no part in the commit's ordered walk.  The header is read once:
+ * everything after the parse works from d_recs.  d_payload_len[i] = len for
+ * REC_OK, else 0.
+ *
+ * After either call d_recs[i] holds the descriptor the call ran (open: what
+ * was parsed).  A REC_MALFORMED record has key_idx = 0xffffffff, len = 0 and
+ * reserved = NOISE_GPU_REC_MALFORMED; its other fields are unspecified.
+ *
+ * NOISE_GPU_E_ARG before any device work: null table, span, span base, d_recs
+ * or d_status; nrec > 2^31; an off array not 8-byte aligned; a len, d_sess,
+ * d_peer or d_*_len array not 4-byte aligned; d_recs not 8-byte aligned; seal
+ * with payload->len == NULL and len_all > NOISE_GPU_DGRAM_MAX_LEN; open with
+ * pkt->len == NULL and len_all outside [32, 32 + NOISE_GPU_DGRAM_MAX_LEN].
+ * nrec == 0 on a table is OK and does nothing. */
+#define NOISE_GPU_DGRAM_HDR 16u
+#define NOISE_GPU_DGRAM_MAX_LEN 65519u
+#define NOISE_GPU_REC_MALFORMED 5u /* packet shorter than 32 bytes, longer than 32 + 65519, wrong
+                                      type; seal: payload longer than 65519 */
+int noise_gpu_dgram_seal(noise_gpu_cs *cs, uint32_t type,
+                         const uint32_t *d_sess,        /* [nrec] session of the SENDER's table       */
+                         const uint32_t *d_peer,        /* [nsess] receiver index per session, or NULL:
+                                                           the session index itself                    */
+                         const noise_gpu_span *payload, /* plaintext: base, off|stride, len|len_all    */
+                         const noise_gpu_span *pkt,     /* packet slots: base, off|stride (len unused) */
+                         noise_gpu_record *d_recs,      /* [nrec] out: the descriptors the call ran    */
+                         uint32_t *d_pkt_len,           /* [nrec] out, may be NULL                     */
+                         uint8_t *d_status,             /* [nrec] out, required                        */
+                         uint64_t len_sum, uint64_t nrec, void *stream);
+int noise_gpu_dgram_open(noise_gpu_cs *cs, uint32_t type,
+                         const noise_gpu_span *pkt,     /* packets: base, off|stride, len|len_all      */
+                         const noise_gpu_span *payload, /* plaintext out: base, off|stride             */
+                         noise_gpu_record *d_recs,      /* [nrec] out: receiver, counter, len, offsets */
+                         uint32_t *d_payload_len,       /* [nrec] out, may be NULL                     */
+                         uint8_t *d_status,             /* [nrec] out, required                        */
+                         uint64_t len_sum, uint64_t nrec, void *stream);
+
 /* ---- host-buffer entry points (synchronous) ----------------------------
  * Used by the CipherState shim for single records (encrypt_with_ad /
  * decrypt_with_ad / rekey).  A record of <= 65535 bytes with <= 8192 bytes of

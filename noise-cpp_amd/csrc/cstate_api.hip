@@ -1,13 +1,14 @@
-// cstate_api.hip -- the noise_gpu_cs_* / noise_gpu_cswin_* C ABI
-// (include/noise_gpu.h): device-resident CipherState tables.  What is here:
-// the table's memory, the argument checks and the grow-only scratch; the
-// sequences of launches behind the composite calls are cstate_calls.hpp's,
-// the kernels cstate_kernels.hip's and cswin_kernels.hip's.  No kernels here.
+// cstate_api.hip -- the noise_gpu_cs_* / noise_gpu_cswin_* / noise_gpu_dgram_*
+// C ABI (include/noise_gpu.h): device-resident CipherState tables.  What is
+// here: the table's memory, the argument checks and the grow-only scratch; the
+// sequences of launches behind the composite calls are cstate_calls.hpp's and
+// dgram_calls.hpp's, the kernels cstate_kernels.hip's, cswin_kernels.hip's and
+// dgram_kernels.hip's.  No kernels here.
 #include <hip/hip_runtime.h>
 
 #include <new>
 
-#include "cstate_calls.hpp"
+#include "dgram_calls.hpp"
 #include "noise_amd/dev_mem.hpp"
 
 using namespace noise_amd;
@@ -163,6 +164,42 @@ int cs_check_sessions(const noise_gpu_cs *cs, bool decrypt, bool windowed, const
     return api_arg_fail("sessions batches need a tile length and 16-byte aligned buffers/strides "
                         "(see noise_gpu_encrypt_sessions)");
   return api_check_device();
+}
+
+// ---- the datagram calls' checks: one per addressing form ----
+// a span's own rules; lens: its lengths are read, within [min_len, max_len]
+int dg_check_span(const noise_gpu_span *s, bool lens, uint32_t min_len, uint32_t max_len, const char *range) {
+  if (!s || !s->base) return api_arg_fail("null span / span base");
+  if (reinterpret_cast<uintptr_t>(s->off) & 7u) return api_arg_fail("span offsets must be 8-byte aligned");
+  if (!lens) return NOISE_GPU_OK;
+  if (reinterpret_cast<uintptr_t>(s->len) & 3u) return api_arg_fail("span lengths must be 4-byte aligned");
+  if (!s->len && (s->len_all < min_len || s->len_all > max_len)) return api_arg_fail(range);
+  return NOISE_GPU_OK;
+}
+
+// the arrays beside the spans (seal: d_sess required, d_peer optional).  The
+// table comes last but for the device, so that every rule above it holds on
+// any table; OK with nrec == 0: nothing to do.
+int dg_check(const noise_gpu_cs *cs, bool seal, const void *d_sess, const void *d_peer,
+             const noise_gpu_span *lens_span, const noise_gpu_span *slots_span, const void *d_recs,
+             const void *d_lens, const void *d_status, uint64_t nrec) {
+  if (nrec > kCsMaxRec) return api_arg_fail("more than 2^31 records in one batch");
+  if (nrec != 0) {
+    int rc = seal ? dg_check_span(lens_span, true, 0, NOISE_GPU_DGRAM_MAX_LEN,
+                                  "payload length above NOISE_GPU_DGRAM_MAX_LEN")
+                  : dg_check_span(lens_span, true, NOISE_GPU_DGRAM_HDR + 16u,
+                                  NOISE_GPU_DGRAM_HDR + 16u + NOISE_GPU_DGRAM_MAX_LEN,
+                                  "packet length outside [32, 32 + NOISE_GPU_DGRAM_MAX_LEN]");
+    if (rc || (rc = dg_check_span(slots_span, false, 0, 0, nullptr))) return rc;
+    if (!d_recs || !d_status) return api_arg_fail("null descriptors / status");
+    if (reinterpret_cast<uintptr_t>(d_recs) & 7u) return api_arg_fail("descriptors must be 8-byte aligned");
+    if (seal && !d_sess) return api_arg_fail("null session array");
+    if ((reinterpret_cast<uintptr_t>(d_sess) | reinterpret_cast<uintptr_t>(d_peer) |
+         reinterpret_cast<uintptr_t>(d_lens)) & 3u)
+      return api_arg_fail("session / peer / length arrays must be 4-byte aligned");
+  }
+  if (!cs) return api_arg_fail("null table");
+  return nrec == 0 ? NOISE_GPU_OK : api_check_device();
 }
 
 // ---- the composite calls: checks, scratch, then cstate_calls.hpp ----
@@ -395,6 +432,38 @@ int noise_gpu_cswin_decrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess,
       [&](const CsColumns &mine) {
         return launch_aead_sessions(true, cs->t.keys, cs->t.nsess, reinterpret_cast<const uint32_t *>(mine.sess),
                                     d_nonces, d_in, in_stride, d_out, out_stride, len, d_status, nrec, st);
+      }));
+}
+
+int noise_gpu_dgram_seal(noise_gpu_cs *cs, uint32_t type, const uint32_t *d_sess, const uint32_t *d_peer,
+                         const noise_gpu_span *payload, const noise_gpu_span *pkt, noise_gpu_record *d_recs,
+                         uint32_t *d_pkt_len, uint8_t *d_status, uint64_t len_sum, uint64_t nrec,
+                         void *stream) {
+  const int rc = dg_check(cs, true, d_sess, d_peer, payload, pkt, d_recs, d_pkt_len, d_status, nrec);
+  if (rc || nrec == 0) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  API_TRY(cs_scratch(cs, cs_scratch_layout(false, true, nrec).total, st));
+  return cs_done(dgram_seal_call(
+      cs->t, type, d_sess, d_peer, *payload, *pkt, d_recs, d_pkt_len, d_status, nrec, cs->scratch, st,
+      [&](const CsColumns &mine) {
+        return launch_aead_records(false, cs->t.keys, cs->t.nsess, mine.recs, nrec, payload->base, pkt->base,
+                                   nullptr, nullptr, st, len_sum);
+      }));
+}
+
+int noise_gpu_dgram_open(noise_gpu_cs *cs, uint32_t type, const noise_gpu_span *pkt,
+                         const noise_gpu_span *payload, noise_gpu_record *d_recs, uint32_t *d_payload_len,
+                         uint8_t *d_status, uint64_t len_sum, uint64_t nrec, void *stream) {
+  const int rc = dg_check(cs, false, nullptr, nullptr, pkt, payload, d_recs, d_payload_len, d_status, nrec);
+  if (rc || nrec == 0) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  API_TRY(cs_window_rows(cs, st));
+  API_TRY(cs_scratch(cs, cs_scratch_layout(true, true, nrec).total, st));
+  return cs_done(dgram_open_call(
+      cs->t, cs->w, type, *pkt, *payload, d_recs, d_payload_len, d_status, nrec, cs->scratch, st,
+      [&](const CsColumns &mine) {
+        return launch_aead_records(true, cs->t.keys, cs->t.nsess, mine.recs, nrec, pkt->base, payload->base,
+                                   nullptr, d_status, st, len_sum);
       }));
 }
 

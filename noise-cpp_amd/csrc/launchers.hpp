@@ -275,6 +275,30 @@ hipError_t launch_cw_finish(const uint8_t *pre, uint8_t *status, const noise_gpu
                             uint8_t *out, uint64_t out_stride, uint32_t len, uint64_t nrec,
                             hipStream_t stream);
 
+// ---- datagram wire format on a table (dgram_kernels.hip) -----------------
+// Packet i: a 16-byte header {LE32 type, LE32 receiver, LE64 counter}, then
+// ct || tag.  Spans as in noise_gpu.h: record i at base + (off ? off[i] :
+// i * stride), len ? len[i] : len_all bytes.  A record kept off the AEAD
+// kernels (open: a malformed packet; seal: a payload over
+// NOISE_GPU_DGRAM_MAX_LEN) has key_idx = 0xffffffff, len = 0 and
+// reserved = NOISE_GPU_REC_MALFORMED in its descriptor; reserved is 0 otherwise.
+// open: recs[i] = {in_off = packet offset + 16, out_off = payload offset,
+// nonce = counter, len = packet length - 32, key_idx = receiver}.  A packet
+// shorter than 32 bytes is not read at all, a longer one up to its header.
+hipError_t launch_dgram_parse(uint32_t type, const noise_gpu_span &pkt, const noise_gpu_span &payload,
+                              noise_gpu_record *recs, uint64_t nrec, hipStream_t stream);
+// seal: recs[i] = {in_off = payload offset, out_off = packet offset + 16,
+// len, key_idx = sess[i]}
+hipError_t launch_dgram_build(const uint32_t *sess, const noise_gpu_span &payload, const noise_gpu_span &pkt,
+                              noise_gpu_record *recs, uint64_t nrec, hipStream_t stream);
+// After the table call.  Marked records: status MALFORMED, length 0.  seal:
+// the header {type, peer ? peer[key_idx] : key_idx, nonce} of every OK record
+// at out + out_off - 16 and lens[i] = 32 + len; open: lens[i] = len for OK.
+// Every other record's length is 0; lens may be null.
+hipError_t launch_dgram_finish(bool seal, uint32_t type, const uint32_t *peer, const noise_gpu_record *recs,
+                               uint8_t *out, uint8_t *status, uint32_t *lens, uint64_t nrec,
+                               hipStream_t stream);
+
 // C-ABI helpers shared by the API translation units (defined in noise_gpu_api.hip).
 // A failure sets the thread's noise_gpu_last_error() text and returns its status
 int api_fail(int status, const char *msg);

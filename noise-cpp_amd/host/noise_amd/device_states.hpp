@@ -156,6 +156,26 @@ class DeviceCipherStates {
                                            d_status, nrec, stream),
           "noise_gpu_cswin_decrypt_sessions");
   }
+  // ---- the datagram wire format (noise_gpu_dgram_*): a packet is the 16-byte
+  // header {LE32 type, LE32 receiver, LE64 counter}, then ct || tag -----------
+  // payloads -> packets of the sessions d_sess[i]; the receiver field is
+  // d_peer[session], or the session itself.  d_recs: room for nrec descriptors
+  void seal(std::uint32_t type, const std::uint32_t *d_sess, const std::uint32_t *d_peer,
+            const noise_gpu_span &payload, const noise_gpu_span &pkt, noise_gpu_record *d_recs,
+            std::uint32_t *d_pkt_len, std::uint8_t *d_status, std::uint64_t nrec, std::uint64_t len_sum = 0,
+            void *stream = nullptr) {
+    check(noise_gpu_dgram_seal(cs_, type, d_sess, d_peer, &payload, &pkt, d_recs, d_pkt_len, d_status, len_sum,
+                               nrec, stream),
+          "noise_gpu_dgram_seal");
+  }
+  // packets -> payloads through the replay windows; malformed packets get
+  // NOISE_GPU_REC_MALFORMED and touch nothing
+  void open(std::uint32_t type, const noise_gpu_span &pkt, const noise_gpu_span &payload,
+            noise_gpu_record *d_recs, std::uint32_t *d_payload_len, std::uint8_t *d_status, std::uint64_t nrec,
+            std::uint64_t len_sum = 0, void *stream = nullptr) {
+    check(noise_gpu_dgram_open(cs_, type, &pkt, &payload, d_recs, d_payload_len, d_status, len_sum, nrec, stream),
+          "noise_gpu_dgram_open");
+  }
   // A host ReplayWindow continuing session s's (migration, like state(s)).
   // Synchronises `stream`.
   [[nodiscard]] ReplayWindow window(std::uint64_t s, void *stream = nullptr) const {

@@ -21,6 +21,8 @@ OK, E_NONCE, E_MAC, E_ARG, E_HIP, E_NODEV = 0, 1, 2, 3, 4, 5
 REC_OK, REC_BAD_MAC, REC_BAD_KEY, REC_NONCE = 0, 1, 2, 3
 REC_REPLAY = 4
 CS_WINDOW = 1024  # nonces per session's replay window (NOISE_GPU_CS_WINDOW)
+REC_MALFORMED = 5  # datagram calls: bad packet length or type, payload over DGRAM_MAX_LEN
+DGRAM_HDR, DGRAM_MAX_LEN = 16, 65519  # header bytes {LE32 type, LE32 receiver, LE64 counter}; payload limit
 NONCE_LIMIT = (1 << 64) - 2  # noise.cpp:398 refuses n == 2^64-2
 
 
@@ -175,6 +177,10 @@ def load(path=LIB_PATH):
         "noise_gpu_cswin_decrypt_records": (ctypes.c_int, [vp, u8p, u64, u8p, u8p, u8p, u8p, u64, vp]),
         "noise_gpu_cswin_decrypt_sessions": (ctypes.c_int, [vp, u8p, u8p, u8p, u64, u8p, u64, u32, u8p,
                                                             u64, vp]),
+        "noise_gpu_dgram_seal": (ctypes.c_int, [vp, u32, u8p, u8p, ctypes.POINTER(Span),
+                                                ctypes.POINTER(Span), u8p, u8p, u8p, u64, u64, vp]),
+        "noise_gpu_dgram_open": (ctypes.c_int, [vp, u32, ctypes.POINTER(Span), ctypes.POINTER(Span), u8p,
+                                                u8p, u8p, u64, u64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -450,6 +456,26 @@ class CipherStateTable:
         _check(self.lib.noise_gpu_cswin_decrypt_sessions(
             self.h, _ptr(d_sess), _ptr(d_nonces), _ptr(d_in), in_stride, _ptr(d_out), out_stride, length,
             _ptr(d_status), nrec, _stream(stream)), "noise_gpu_cswin_decrypt_sessions")
+
+    # ---- the datagram wire format (noise_gpu_dgram_*): packets are a 16-byte
+    # header {type, receiver, counter}, then ct || tag
+    def seal_datagrams(self, type_, d_sess, payload, pkt, d_recs, d_status, nrec, d_peer=None,
+                       d_pkt_len=None, len_sum=0, stream=None):
+        """payload / pkt: span()s; d_sess: int32 sessions of this table; d_peer:
+        int32 receiver index per session (None: the session index); d_recs: room
+        for nrec descriptors (out); d_pkt_len: int32 (out, optional)."""
+        _check(self.lib.noise_gpu_dgram_seal(
+            self.h, type_, _ptr(d_sess), _ptr(d_peer), ctypes.byref(payload), ctypes.byref(pkt),
+            _ptr(d_recs), _ptr(d_pkt_len), _ptr(d_status), len_sum, nrec, _stream(stream)),
+            "noise_gpu_dgram_seal")
+
+    def open_datagrams(self, type_, pkt, payload, d_recs, d_status, nrec, d_payload_len=None,
+                       len_sum=0, stream=None):
+        """pkt (with lengths) / payload: span()s; d_recs: room for nrec
+        descriptors (out: receiver, counter, len, offsets); windowed receive."""
+        _check(self.lib.noise_gpu_dgram_open(
+            self.h, type_, ctypes.byref(pkt), ctypes.byref(payload), _ptr(d_recs), _ptr(d_payload_len),
+            _ptr(d_status), len_sum, nrec, _stream(stream)), "noise_gpu_dgram_open")
 
 
 # ---- host-buffer entry points (CipherState single-record path) ------------
