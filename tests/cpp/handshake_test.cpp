@@ -5,6 +5,7 @@
 //   handshake_test hmac <keyhex> <hex>       HMAC-BLAKE2b
 //   handshake_test hkdf <ckhex> <ikmhex>     Noise HKDF, 3 outputs
 //   handshake_test x25519 <skhex> <uhex>     X25519
+//   handshake_test verify <ahex> <bhex> ...  noise::crypto::verify of each pair: 1 / 0
 //   handshake_test patterns                  every enum pattern name, message count
 //       (the above need no GPU: tests/test_handshake.py)
 //   handshake_test vectors <tsv>             replay tests/golden/handshake_vectors.tsv
@@ -952,6 +953,12 @@ int main(int argc, char **argv) {
       std::printf("%s %s %s\n", hex(o1).c_str(), hex(o2).c_str(), hex(o3).c_str());
     } else if (cmd == "x25519" && argc == 4) {
       std::printf("%s\n", hex(noise::crypto::x25519(a32(argv[2]), a32(argv[3]))).c_str());
+    } else if (cmd == "verify" && argc >= 4 && argc % 2 == 0) {
+      for (int i = 2; i + 1 < argc; i += 2) {  // one verdict per pair, in order
+        const bytes a = unhex(argv[i]), b = unhex(argv[i + 1]);
+        if (a.size() != b.size()) throw std::runtime_error("verify: lengths differ");
+        std::printf("%d\n", noise::crypto::verify(a.data(), b.data(), a.size()) ? 1 : 0);
+      }
     } else if (cmd == "patterns") {
       for (int p = 0; p <= (int)noise::HandshakePattern::IXpsk2; ++p)
         std::printf("%s\n", std::string(noise::pattern_name((noise::HandshakePattern)p)).c_str());

@@ -76,6 +76,27 @@ def test_x25519_vs_python_ladder():
         assert run("x25519", sk.hex(), u.hex())[0] == make_fixtures.x25519(sk, u).hex()
 
 
+@pytest.mark.parametrize("n", [16, 32, 64])
+def test_constant_time_verify_sees_every_bit(n):
+    """noise::crypto::verify (host/crypto.cpp), the host's tag / key compare:
+    equal strings verify, and a flip of any single bit of either does not --
+    16 bytes is a tag, 32 a key, 64 a hash.  (No host decrypt calls it today:
+    the host CipherState takes its verdict from the GPU, whose compare
+    tests/test_gpu_tag_bits.py sweeps; this pins the function for the day a
+    host path does.)"""
+    rng = random.Random(0x7E51 + n)
+    a = bytes(rng.getrandbits(8) for _ in range(n))
+    pairs, want = [a.hex(), a.hex()], ["1"]
+    for b in range(8 * n):
+        t = bytearray(a)
+        t[b >> 3] ^= 1 << (b & 7)
+        pairs += [a.hex(), t.hex(), t.hex(), a.hex()]
+        want += ["0", "0"]
+    pairs += [bytes(n).hex(), bytes(n).hex(), (b"\xff" * n).hex(), (b"\xff" * n).hex()]
+    want += ["1", "1"]
+    assert run("verify", *pairs) == want
+
+
 def test_pattern_names_match_reference_enum():
     # noise.h:21-81 of the reference, in order
     ref = ("IK IN IX K KK KN KX N NK NN NX XK XN XX NK1 NX1 X X1K XK1 X1K1 X1N X1X XX1 X1X1 "
