@@ -594,6 +594,105 @@ int noise_gpu_dgram_open(noise_gpu_cs *cs, uint32_t type,
                          uint8_t *d_status,             /* [nrec] out, required                        */
                          uint64_t len_sum, uint64_t nrec, void *stream);
 
+/* ---- length-prefixed stream framing on a table: seal and open --------------
+ * Noise over a byte stream (TCP): connection j carries a concatenation of
+ * frames
+ *   BE16(L) || ct || tag      L = len + 16, 16 <= L <= 65535, 0 <= len <= 65519
+ * where ct || tag is the transport message under the session's key and its
+ * in-order nonce n, no AD: the byte stream noise::transport::append_frame makes
+ * of CipherState::encrypt_with_ad outputs and noise::transport::Deframer takes
+ * apart.  Spans as above, with i the connection.  Both calls are asynchronous
+ * on `stream`, never synchronise with the host, obey the table's
+ * one-stream-at-a-time contract and use the table's scratch only.  A session
+ * may appear on more than one connection: its records are ordered by
+ * connection first.  len_sum is the hint of the _sized calls.
+ *
+ * open gives every connection the result of these loops:
+ *   1. walk connection j, avail = len[j], pos = 0:
+ *        avail - pos < 2      -> stop (a partial length)
+ *        L = BE16 at pos; L < 16 -> stop, BAD_LEN (the frame is not consumed)
+ *        avail - pos - 2 < L  -> stop (a partial frame)
+ *        else a frame; pos += 2 + L
+ *      No byte at or beyond wire offset + len[j] is read: a single trailing
+ *      byte is not read as half of a length.
+ *   2. count[j] = the frames found; first[j] = min(sum of count[0..j), max_rec);
+ *      nframes[j] = min(count[j], max_rec - first[j]); *d_total = sum of count.
+ *      A connection that loses frames to the cap is FULL (over BAD_LEN: the
+ *      bad frame was not reached).
+ *   3. frame k of connection j is record first[j] + k: key_idx = d_sess[j],
+ *      in_off = the frame's offset + 2, len = L - 16, out_off = the plain offset
+ *      of j + the sum of its earlier taken frames' len (a contiguous plaintext
+ *      stream; a position never depends on a verdict).  plain == NULL: out_off
+ *      = in_off and the output base is the wire's (each record decrypts in
+ *      place where its ciphertext lies; d_recs says where).
+ *   4. noise_gpu_cs_decrypt_records on those records in slot order: REC_OK /
+ *      _BAD_MAC / _BAD_KEY / _NONCE, counters, copy-zeroing and
+ *      in-place-untouched as that call defines.
+ *   5. slots [sum of nframes, max_rec): status NOISE_GPU_REC_EMPTY, key_idx =
+ *      0xffffffff, len = 0, reserved = NOISE_GPU_REC_EMPTY.
+ *   6. d_consumed[j] = the wire bytes of the taken frames (the host keeps
+ *      len[j] - consumed bytes for the next call), d_plain_len[j] = the sum of
+ *      their len, d_first_bad[j] = the index within the connection of the first
+ *      record whose status is not REC_OK, or nframes[j].
+ * With plain given, the wire and plain ranges of a batch must not overlap.
+ *
+ * seal: count[j] = ceil(len[j] / max_payload) (an empty message makes no
+ * frame), slots as in open; frame k has its plaintext at the msg offset + k *
+ * max_payload, len = min(max_payload, len[j] - k * max_payload) and out_off =
+ * wire offset + k * (max_payload + 18) + 2.  noise_gpu_cs_encrypt_records runs
+ * on them; for every REC_OK record BE16(len + 16) is written in front of its
+ * ciphertext, for any other status nothing at all is written to the frame.  A
+ * connection's refused records (BAD_KEY / NONCE) are a suffix: d_msg_used[j] /
+ * d_wire_len[j] are the plaintext / wire bytes of the OK prefix, and REFUSED is
+ * reported where that prefix is shorter than nframes[j] (over FULL).  The msg
+ * and wire ranges must not overlap.
+ *
+ * The table call runs over all max_rec slots (its record count comes from the
+ * host): the cost scales with max_rec, not with the frames present.  A frame's
+ * ciphertext lies 2 bytes behind the previous tag, so the records are not
+ * 16-byte aligned and take the records kernels' generic class.
+ *
+ * NOISE_GPU_E_ARG before any device work: null table, d_sess, span, span base,
+ * d_recs, d_status or a required per-connection array; nconn or max_rec >
+ * 2^31; max_rec == 0 with nconn > 0; max_payload outside 1 .. 65519; an off
+ * array not 8-byte aligned; len, d_sess or a 4-byte output array not 4-byte
+ * aligned; an 8-byte output array or d_recs not 8-byte aligned.  wire->len ==
+ * NULL is allowed (len_all applies).  nconn == 0 on a table is OK and does
+ * nothing.
+ *
+ * The names are noise_gpu_framed_*: the noise_gpu_cs_* prefix names the closed
+ * set of in-order table calls. */
+#define NOISE_GPU_REC_EMPTY 6u      /* d_recs slot beyond the frames the call took */
+#define NOISE_GPU_FRAMED_OK 0u      /* per connection */
+#define NOISE_GPU_FRAMED_BAD_LEN 1u /* open: stopped at a frame with L < 16 */
+#define NOISE_GPU_FRAMED_FULL 2u    /* stopped because max_rec slots ran out */
+#define NOISE_GPU_FRAMED_REFUSED 3u /* seal: a record was refused (BAD_KEY / NONCE) */
+int noise_gpu_framed_open(noise_gpu_cs *cs,
+                          const uint32_t *d_sess,      /* [nconn] session of each connection               */
+                          const noise_gpu_span *wire,  /* received bytes: base, off|stride, len|len_all    */
+                          const noise_gpu_span *plain, /* plaintext out: base, off|stride; NULL = in place */
+                          noise_gpu_record *d_recs,    /* [max_rec] out: the descriptors the call ran      */
+                          uint8_t *d_status,           /* [max_rec] out, required                          */
+                          uint64_t max_rec,
+                          uint64_t *d_first,           /* [nconn] out, may be NULL: slot of its first frame */
+                          uint32_t *d_nframes,         /* [nconn] out, required: frames taken              */
+                          uint32_t *d_first_bad,       /* [nconn] out, may be NULL                         */
+                          uint64_t *d_consumed,        /* [nconn] out, required: wire bytes of taken frames */
+                          uint64_t *d_plain_len,       /* [nconn] out, may be NULL                         */
+                          uint8_t *d_conn_status,      /* [nconn] out, required                            */
+                          uint64_t *d_total,           /* [1] out, may be NULL: complete frames present    */
+                          uint64_t len_sum, uint64_t nconn, void *stream);
+int noise_gpu_framed_seal(noise_gpu_cs *cs, const uint32_t *d_sess,
+                          const noise_gpu_span *msg,   /* application bytes, any length 0 .. 2^32-1        */
+                          const noise_gpu_span *wire,  /* frames out: base, off|stride (len unused)        */
+                          uint32_t max_payload,        /* 1 .. 65519: plaintext bytes per record           */
+                          noise_gpu_record *d_recs, uint8_t *d_status, uint64_t max_rec,
+                          uint64_t *d_first, uint32_t *d_nframes,
+                          uint64_t *d_msg_used,        /* [nconn] out, required: plaintext bytes sealed    */
+                          uint64_t *d_wire_len,        /* [nconn] out, required: wire bytes written        */
+                          uint8_t *d_conn_status, uint64_t *d_total,
+                          uint64_t len_sum, uint64_t nconn, void *stream);
+
 /* ---- host-buffer entry points (synchronous) ----------------------------
  * Used by the CipherState shim for single records (encrypt_with_ad /
  * decrypt_with_ad / rekey).  A record of <= 65535 bytes with <= 8192 bytes of

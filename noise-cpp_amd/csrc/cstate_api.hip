@@ -1,14 +1,16 @@
-// cstate_api.hip -- the noise_gpu_cs_* / noise_gpu_cswin_* / noise_gpu_dgram_*
-// C ABI (include/noise_gpu.h): device-resident CipherState tables.  What is
-// here: the table's memory, the argument checks and the grow-only scratch; the
-// sequences of launches behind the composite calls are cstate_calls.hpp's and
-// dgram_calls.hpp's, the kernels cstate_kernels.hip's, cswin_kernels.hip's and
-// dgram_kernels.hip's.  No kernels here.
+// cstate_api.hip -- the noise_gpu_cs_* / noise_gpu_cswin_* / noise_gpu_dgram_* /
+// noise_gpu_framed_* C ABI (include/noise_gpu.h): device-resident CipherState
+// tables.  What is here: the table's memory, the argument checks and the
+// grow-only scratch; the sequences of launches behind the composite calls are
+// cstate_calls.hpp's, dgram_calls.hpp's and framed_calls.hpp's, the kernels
+// cstate_kernels.hip's, cswin_kernels.hip's, dgram_kernels.hip's and
+// framed_kernels.hip's.  No kernels here.
 #include <hip/hip_runtime.h>
 
 #include <new>
 
 #include "dgram_calls.hpp"
+#include "framed_calls.hpp"
 #include "noise_amd/dev_mem.hpp"
 
 using namespace noise_amd;
@@ -200,6 +202,41 @@ int dg_check(const noise_gpu_cs *cs, bool seal, const void *d_sess, const void *
   }
   if (!cs) return api_arg_fail("null table");
   return nrec == 0 ? NOISE_GPU_OK : api_check_device();
+}
+
+// ---- the stream-framing calls' checks ----
+// src: the span whose lengths are read (open: wire, seal: msg); dst: open's
+// plain (may be null: in place) or seal's wire.  Beside d_nframes and
+// d_conn_status, the per-connection arrays by width: opt4 (open's
+// d_first_bad), req8a (d_consumed / d_msg_used) and req8b (d_plain_len /
+// d_wire_len, required in seal).  The table comes last but for the device; OK
+// with nconn == 0: nothing to do.
+int fr_check(const noise_gpu_cs *cs, bool seal, const void *d_sess, const noise_gpu_span *src,
+             const noise_gpu_span *dst, uint32_t max_payload, const void *d_recs, const void *d_status,
+             uint64_t max_rec, const void *d_first, const void *d_nframes, const void *opt4, const void *req8a,
+             const void *req8b, bool b_required, const void *d_conn_status, const void *d_total, uint64_t nconn) {
+  if (nconn > kCsMaxRec) return api_arg_fail("more than 2^31 connections in one batch");
+  if (max_rec > kCsMaxRec) return api_arg_fail("more than 2^31 record slots in one batch");
+  if (seal && (max_payload == 0 || max_payload > kFramedMaxLen))
+    return api_arg_fail("max_payload outside 1 .. 65519");
+  if (nconn != 0) {
+    if (max_rec == 0) return api_arg_fail("max_rec is 0 with connections to serve");
+    int rc = dg_check_span(src, true, 0, 0xffffffffu, nullptr);
+    if (rc || ((seal || dst) && (rc = dg_check_span(dst, false, 0, 0, nullptr)))) return rc;
+    if (!d_recs || !d_status) return api_arg_fail("null descriptors / status");
+    if (reinterpret_cast<uintptr_t>(d_recs) & 7u) return api_arg_fail("descriptors must be 8-byte aligned");
+    if (!d_sess) return api_arg_fail("null session array");
+    if (!d_nframes || !req8a || (b_required && !req8b) || !d_conn_status)
+      return api_arg_fail("null per-connection output array");
+    if ((reinterpret_cast<uintptr_t>(d_sess) | reinterpret_cast<uintptr_t>(d_nframes) |
+         reinterpret_cast<uintptr_t>(opt4)) & 3u)
+      return api_arg_fail("session / frame-count arrays must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_first) | reinterpret_cast<uintptr_t>(req8a) |
+         reinterpret_cast<uintptr_t>(req8b) | reinterpret_cast<uintptr_t>(d_total)) & 7u)
+      return api_arg_fail("slot / byte-count arrays must be 8-byte aligned");
+  }
+  if (!cs) return api_arg_fail("null table");
+  return nconn == 0 ? NOISE_GPU_OK : api_check_device();
 }
 
 // ---- the composite calls: checks, scratch, then cstate_calls.hpp ----
@@ -464,6 +501,45 @@ int noise_gpu_dgram_open(noise_gpu_cs *cs, uint32_t type, const noise_gpu_span *
       [&](const CsColumns &mine) {
         return launch_aead_records(true, cs->t.keys, cs->t.nsess, mine.recs, nrec, pkt->base, payload->base,
                                    nullptr, d_status, st, len_sum);
+      }));
+}
+
+int noise_gpu_framed_open(noise_gpu_cs *cs, const uint32_t *d_sess, const noise_gpu_span *wire,
+                          const noise_gpu_span *plain, noise_gpu_record *d_recs, uint8_t *d_status,
+                          uint64_t max_rec, uint64_t *d_first, uint32_t *d_nframes, uint32_t *d_first_bad,
+                          uint64_t *d_consumed, uint64_t *d_plain_len, uint8_t *d_conn_status,
+                          uint64_t *d_total, uint64_t len_sum, uint64_t nconn, void *stream) {
+  const int rc = fr_check(cs, false, d_sess, wire, plain, 0, d_recs, d_status, max_rec, d_first, d_nframes,
+                          d_first_bad, d_consumed, d_plain_len, false, d_conn_status, d_total, nconn);
+  if (rc || nconn == 0) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  API_TRY(cs_scratch(cs, framed_scratch_layout(nconn, max_rec).total, st));
+  const FramedOut out{d_first, d_nframes, d_first_bad, d_consumed, d_plain_len, d_conn_status, d_total};
+  uint8_t *d_out = plain ? plain->base : wire->base;
+  return cs_done(framed_open_call(
+      cs->t, d_sess, *wire, plain, d_recs, d_status, max_rec, out, nconn, cs->scratch, st,
+      [&](const CsColumns &mine) {
+        return launch_aead_records(true, cs->t.keys, cs->t.nsess, mine.recs, max_rec, wire->base, d_out, nullptr,
+                                   d_status, st, len_sum);
+      }));
+}
+
+int noise_gpu_framed_seal(noise_gpu_cs *cs, const uint32_t *d_sess, const noise_gpu_span *msg,
+                          const noise_gpu_span *wire, uint32_t max_payload, noise_gpu_record *d_recs,
+                          uint8_t *d_status, uint64_t max_rec, uint64_t *d_first, uint32_t *d_nframes,
+                          uint64_t *d_msg_used, uint64_t *d_wire_len, uint8_t *d_conn_status,
+                          uint64_t *d_total, uint64_t len_sum, uint64_t nconn, void *stream) {
+  const int rc = fr_check(cs, true, d_sess, msg, wire, max_payload, d_recs, d_status, max_rec, d_first, d_nframes,
+                          nullptr, d_msg_used, d_wire_len, true, d_conn_status, d_total, nconn);
+  if (rc || nconn == 0) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  API_TRY(cs_scratch(cs, framed_scratch_layout(nconn, max_rec).total, st));
+  const FramedOut out{d_first, d_nframes, nullptr, d_msg_used, d_wire_len, d_conn_status, d_total};
+  return cs_done(framed_seal_call(
+      cs->t, d_sess, *msg, *wire, max_payload, d_recs, d_status, max_rec, out, nconn, cs->scratch, st,
+      [&](const CsColumns &mine) {
+        return launch_aead_records(false, cs->t.keys, cs->t.nsess, mine.recs, max_rec, msg->base, wire->base,
+                                   nullptr, nullptr, st, len_sum);
       }));
 }
 

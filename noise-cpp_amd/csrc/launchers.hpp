@@ -299,6 +299,53 @@ hipError_t launch_dgram_finish(bool seal, uint32_t type, const uint32_t *peer, c
                                uint8_t *out, uint8_t *status, uint32_t *lens, uint64_t nrec,
                                hipStream_t stream);
 
+// ---- length-prefixed stream framing on a table (framed_kernels.hip) --------
+// Connection j carries frames BE16(L) || ct || tag, L = len + 16 (noise_gpu.h).
+// count[j] frames (open: the chain walked, seal: ceil(len / max_payload)) get
+// the slots [first[j], first[j] + nframes[j]) of recs in connection order.
+// The launches of one call, in order: count, scan, emit, the table call over
+// all max_rec slots, finish.
+constexpr uint32_t kFramedMaxLen = 65519u;  // plaintext bytes of a frame: L <= 65535
+// the per-connection outputs of noise_gpu_framed_open / _seal
+struct FramedOut {
+  uint64_t *first;       // may be null
+  uint32_t *nframes;
+  uint32_t *first_bad;   // open; may be null
+  uint64_t *bytes_in;    // open: d_consumed; seal: d_msg_used
+  uint64_t *bytes_out;   // open: d_plain_len, may be null; seal: d_wire_len
+  uint8_t *conn_status;
+  uint64_t *total;       // [1], may be null
+};
+// the call's own columns (framed_scratch_layout, framed_calls.hpp)
+struct FramedColumns {
+  uint32_t *count;  // [nconn] frames found / needed
+  uint32_t *first;  // [nconn] first slot, <= max_rec
+  uint64_t *part;   // [ceil(nconn / 64) + 1] sums of count per 64 connections, scanned in place; then the total
+};
+inline uint64_t framed_tiles(uint64_t nconn) { return (nconn + 63) / 64; }
+// count[j], and part[t] = the sum over connections [64 t, 64 t + 64).  open
+// reads src's bytes (never at or beyond a connection's length); seal only lengths.
+hipError_t launch_framed_count(bool open, const noise_gpu_span &src, uint32_t max_payload,
+                               const FramedColumns &c, uint64_t nconn, hipStream_t stream);
+// part: the exclusive scan in place, part[ntiles] = *total (if given) = the sum
+hipError_t launch_framed_scan(uint64_t *part, uint64_t ntiles, uint64_t *total, hipStream_t stream);
+// the descriptors of the taken frames (reserved = 0), the EMPTY marks of the
+// slots behind them (key_idx = 0xffffffff, len = 0, reserved =
+// NOISE_GPU_REC_EMPTY), c.first, and of `out`: first, nframes, conn_status
+// (OK / FULL / open's BAD_LEN), total, and open's bytes_in / bytes_out.  dst
+// null (open only): in place, out_off = in_off.
+hipError_t launch_framed_emit(bool open, const uint32_t *sess, const noise_gpu_span &src,
+                              const noise_gpu_span *dst, uint32_t max_payload, noise_gpu_record *recs,
+                              uint64_t max_rec, const FramedColumns &c, const FramedOut &out, uint64_t nconn,
+                              hipStream_t stream);
+// After the table call.  Marked slots: status EMPTY.  seal: BE16(len + 16) in
+// front of every OK record's ciphertext in `wire`; per connection the OK
+// prefix's bytes_in / bytes_out, and REFUSED where it is shorter than nframes.
+// open: first_bad (if given).
+hipError_t launch_framed_finish(bool seal, const noise_gpu_record *recs, uint8_t *status, uint64_t max_rec,
+                                uint8_t *wire, const FramedColumns &c, const FramedOut &out, uint64_t nconn,
+                                hipStream_t stream);
+
 // C-ABI helpers shared by the API translation units (defined in noise_gpu_api.hip).
 // A failure sets the thread's noise_gpu_last_error() text and returns its status
 int api_fail(int status, const char *msg);

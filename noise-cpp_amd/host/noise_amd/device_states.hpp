@@ -176,6 +176,42 @@ class DeviceCipherStates {
     check(noise_gpu_dgram_open(cs_, type, &pkt, &payload, d_recs, d_payload_len, d_status, len_sum, nrec, stream),
           "noise_gpu_dgram_open");
   }
+  // ---- length-prefixed stream framing (noise_gpu_framed_*): connection j
+  // carries frames BE16(len + 16) || ct || tag, what transport::append_frame
+  // writes and transport::Deframer reads --------------------------------------
+  // the per-connection outputs; nframes, bytes_in, bytes_out (seal) and
+  // conn_status are required
+  struct FramedOut {
+    std::uint64_t *d_first = nullptr;
+    std::uint32_t *d_nframes = nullptr;
+    std::uint32_t *d_first_bad = nullptr;   // open
+    std::uint64_t *d_bytes_in = nullptr;    // open: d_consumed; seal: d_msg_used
+    std::uint64_t *d_bytes_out = nullptr;   // open: d_plain_len; seal: d_wire_len
+    std::uint8_t *d_conn_status = nullptr;  // NOISE_GPU_FRAMED_*
+    std::uint64_t *d_total = nullptr;
+  };
+  // messages -> frames of at most max_payload plaintext bytes, frame k of a
+  // connection at its wire offset + k * (max_payload + 18)
+  void framed_seal(const std::uint32_t *d_sess, const noise_gpu_span &msg, const noise_gpu_span &wire,
+                   std::uint32_t max_payload, noise_gpu_record *d_recs, std::uint8_t *d_status,
+                   std::uint64_t max_rec, const FramedOut &out, std::uint64_t nconn, std::uint64_t len_sum = 0,
+                   void *stream = nullptr) {
+    check(noise_gpu_framed_seal(cs_, d_sess, &msg, &wire, max_payload, d_recs, d_status, max_rec, out.d_first,
+                                out.d_nframes, out.d_bytes_in, out.d_bytes_out, out.d_conn_status, out.d_total,
+                                len_sum, nconn, stream),
+          "noise_gpu_framed_seal");
+  }
+  // the complete frames of every connection's bytes -> one plaintext stream per
+  // connection (plain null: each record in place), in-order nonces
+  void framed_open(const std::uint32_t *d_sess, const noise_gpu_span &wire, const noise_gpu_span *plain,
+                   noise_gpu_record *d_recs, std::uint8_t *d_status, std::uint64_t max_rec,
+                   const FramedOut &out, std::uint64_t nconn, std::uint64_t len_sum = 0,
+                   void *stream = nullptr) {
+    check(noise_gpu_framed_open(cs_, d_sess, &wire, plain, d_recs, d_status, max_rec, out.d_first, out.d_nframes,
+                                out.d_first_bad, out.d_bytes_in, out.d_bytes_out, out.d_conn_status,
+                                out.d_total, len_sum, nconn, stream),
+          "noise_gpu_framed_open");
+  }
   // A host ReplayWindow continuing session s's (migration, like state(s)).
   // Synchronises `stream`.
   [[nodiscard]] ReplayWindow window(std::uint64_t s, void *stream = nullptr) const {

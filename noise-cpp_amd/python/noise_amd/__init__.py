@@ -23,6 +23,10 @@ REC_REPLAY = 4
 CS_WINDOW = 1024  # nonces per session's replay window (NOISE_GPU_CS_WINDOW)
 REC_MALFORMED = 5  # datagram calls: bad packet length or type, payload over DGRAM_MAX_LEN
 DGRAM_HDR, DGRAM_MAX_LEN = 16, 65519  # header bytes {LE32 type, LE32 receiver, LE64 counter}; payload limit
+REC_EMPTY = 6  # stream-framing calls: a d_recs slot beyond the frames the call took
+# per connection (noise_gpu_framed_*): open stopped at a length < 16; max_rec slots ran out; seal: a record refused
+FRAMED_OK, FRAMED_BAD_LEN, FRAMED_FULL, FRAMED_REFUSED = 0, 1, 2, 3
+FRAMED_MAX_PAYLOAD = 65519  # plaintext bytes of one frame: BE16(len + 16) <= 65535
 NONCE_LIMIT = (1 << 64) - 2  # noise.cpp:398 refuses n == 2^64-2
 
 
@@ -181,6 +185,10 @@ def load(path=LIB_PATH):
                                                 ctypes.POINTER(Span), u8p, u8p, u8p, u64, u64, vp]),
         "noise_gpu_dgram_open": (ctypes.c_int, [vp, u32, ctypes.POINTER(Span), ctypes.POINTER(Span), u8p,
                                                 u8p, u8p, u64, u64, vp]),
+        "noise_gpu_framed_open": (ctypes.c_int, [vp, u8p, ctypes.POINTER(Span), ctypes.POINTER(Span), u8p, u8p,
+                                                 u64, u8p, u8p, u8p, u8p, u8p, u8p, u8p, u64, u64, vp]),
+        "noise_gpu_framed_seal": (ctypes.c_int, [vp, u8p, ctypes.POINTER(Span), ctypes.POINTER(Span), u32, u8p,
+                                                 u8p, u64, u8p, u8p, u8p, u8p, u8p, u8p, u64, u64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -476,6 +484,30 @@ class CipherStateTable:
         _check(self.lib.noise_gpu_dgram_open(
             self.h, type_, ctypes.byref(pkt), ctypes.byref(payload), _ptr(d_recs), _ptr(d_payload_len),
             _ptr(d_status), len_sum, nrec, _stream(stream)), "noise_gpu_dgram_open")
+
+    # ---- length-prefixed stream framing (noise_gpu_framed_*): connection j
+    # carries frames BE16(len + 16) || ct || tag
+    def open_framed(self, d_sess, wire, d_recs, d_status, max_rec, d_nframes, d_consumed, d_conn_status,
+                    nconn, plain=None, d_first=None, d_first_bad=None, d_plain_len=None, d_total=None,
+                    len_sum=0, stream=None):
+        """wire (with lengths) / plain: span()s, plain None = in place; d_sess:
+        int32 session per connection; d_recs / d_status: room for max_rec (out);
+        d_nframes, d_first_bad: int32; d_first, d_consumed, d_plain_len, d_total:
+        int64; d_conn_status: uint8 (FRAMED_*)."""
+        _check(self.lib.noise_gpu_framed_open(
+            self.h, _ptr(d_sess), ctypes.byref(wire), ctypes.byref(plain) if plain is not None else None,
+            _ptr(d_recs), _ptr(d_status), max_rec, _ptr(d_first), _ptr(d_nframes), _ptr(d_first_bad),
+            _ptr(d_consumed), _ptr(d_plain_len), _ptr(d_conn_status), _ptr(d_total), len_sum, nconn,
+            _stream(stream)), "noise_gpu_framed_open")
+
+    def seal_framed(self, d_sess, msg, wire, max_payload, d_recs, d_status, max_rec, d_nframes, d_msg_used,
+                    d_wire_len, d_conn_status, nconn, d_first=None, d_total=None, len_sum=0, stream=None):
+        """msg (with lengths) / wire: span()s; frame k of a connection lies at
+        its wire offset + k * (max_payload + 18); arrays as open_framed."""
+        _check(self.lib.noise_gpu_framed_seal(
+            self.h, _ptr(d_sess), ctypes.byref(msg), ctypes.byref(wire), max_payload, _ptr(d_recs),
+            _ptr(d_status), max_rec, _ptr(d_first), _ptr(d_nframes), _ptr(d_msg_used), _ptr(d_wire_len),
+            _ptr(d_conn_status), _ptr(d_total), len_sum, nconn, _stream(stream)), "noise_gpu_framed_seal")
 
 
 # ---- host-buffer entry points (CipherState single-record path) ------------
