@@ -419,6 +419,59 @@ int noise_gpu_cs_decrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess, cons
                                   uint64_t in_stride, uint8_t *d_out, uint64_t out_stride,
                                   uint32_t len, uint8_t *d_status, uint64_t nrec, void *stream);
 
+/* ---- in-band rekey schedule on a table ------------------------------------
+ * "Rekey after every R messages" (Noise spec 4.2, 11.3) is a pure function of
+ * the counter, and the counters live on the device: a table has one schedule,
+ * `every`, that the in-order calls apply on the GPU where they assign the
+ * nonces -- inside a batch, stream-ordered, with no host synchronisation and
+ * no per-record host work.  0 = off, the state after create.  With every != 0
+ * each session behaves exactly like this loop around a host CipherState
+ * (noise.cpp:393-439), run over its records in record order:
+ *
+ *   status = encrypt_with_ad / decrypt_with_ad(record)
+ *            -- as above: refused at n == 2^64-2, a keyless session does nothing
+ *   if the call moved n (an accepted record, whatever its tag did on decrypt):
+ *       if n % every == 0:       -- n AFTER the move, wrapped mod 2^64
+ *           rekey()              -- k <- ENCRYPT(k, 2^64-2, "", 0^32)[0..32), n untouched
+ *
+ * So for a session with counter n0 at entry, the record of rank r (nonce
+ * n0 + r) runs under REKEY^g(k0), g = #{ j in 1..r : (n0 + j) mod 2^64 is a
+ * multiple of every }; after the batch the key row is REKEY^G(k0), G the same
+ * count over 1..accepted, and the counter ends where it ends without a
+ * schedule.  A boundary hit by the last accepted record of a batch moves the
+ * row although no record of that batch uses the new key.  n0 = 2^64-1 wraps to
+ * 0, a multiple of every `every`.  Refused records (NOISE_GPU_REC_NONCE) and
+ * keyless or out-of-range sessions move nothing.  noise_gpu_cs_set with keys
+ * installs "the key for counter n" and remembers no generation;
+ * noise_gpu_cs_rekey applies one more REKEY; noise_gpu_cs_get returns the
+ * current row.  Both peers must set the same `every`.
+ *
+ * Honour the schedule: noise_gpu_cs_{en,de}crypt_records,
+ * noise_gpu_cs_{en,de}crypt_sessions, noise_gpu_framed_seal and
+ * noise_gpu_framed_open.  Every other output of these calls (statuses, the
+ * nonces in d_recs, counters, the framed per-connection arrays, what is and is
+ * not written to the outputs) is as documented without a schedule.
+ *
+ * Refuse a table whose every != 0 with NOISE_GPU_E_ARG, after their argument
+ * checks and before any device work: noise_gpu_cs_assign (it hands out nonces,
+ * and cannot hand out the keys that go with them), every noise_gpu_cswin_*
+ * call (REKEY is one-way: an out-of-order receiver cannot go back a generation
+ * for a late packet) and noise_gpu_dgram_seal / noise_gpu_dgram_open (a
+ * datagram nobody can open is not sealed).  They work again after
+ * noise_gpu_csrekey_set(cs, 0).  A windowed schedule with retained generations
+ * does not exist.
+ *
+ * Cost and hygiene: a scheduled call keeps the keys of the generations its
+ * records run under in 32 * nrec bytes of the table's scratch, and zeroes them
+ * stream-ordered at the end of the call (old generations are what rekeying
+ * exists to erase).  A session's chain is serial: accepted / every ChaCha20
+ * blocks in one lane, one lane per touched session.  every = 1 is legal, and
+ * a batch of c records of one session then costs c dependent blocks. */
+/* 0 = off (default).  Applies to calls issued after it; a host-side attribute,
+ * no device work. */
+int noise_gpu_csrekey_set(noise_gpu_cs *cs, uint64_t every);
+int noise_gpu_csrekey_get(const noise_gpu_cs *cs, uint64_t *every);
+
 /* ---- out-of-order receive on a table: replay windows ---------------------
  * For datagram transports (Noise spec 11.4): the sender puts n on the wire
  * (noise_gpu_cs_encrypt_records writes the assigned nonces into the

@@ -1,5 +1,5 @@
-// cstate_api.hip -- the noise_gpu_cs_* / noise_gpu_cswin_* / noise_gpu_dgram_* /
-// noise_gpu_framed_* C ABI (include/noise_gpu.h): device-resident CipherState
+// cstate_api.hip -- the noise_gpu_cs_* / noise_gpu_csrekey_* / noise_gpu_cswin_* /
+// noise_gpu_dgram_* / noise_gpu_framed_* C ABI (include/noise_gpu.h): device-resident CipherState
 // tables.  What is here: the table's memory, the argument checks and the
 // grow-only scratch; the sequences of launches behind the composite calls are
 // cstate_calls.hpp's, dgram_calls.hpp's and framed_calls.hpp's, the kernels
@@ -115,6 +115,14 @@ hipError_t cs_window_rows(noise_gpu_cs *cs, hipStream_t st) {
 }
 
 // ---- argument checks ----
+// the calls a table with a rekey schedule refuses, after their own checks and
+// before any device work
+int cs_check_unscheduled(const noise_gpu_cs *cs) {
+  if (cs->t.every == 0) return NOISE_GPU_OK;
+  return api_arg_fail("the table has a rekey schedule (noise_gpu_csrekey_set): only the in-order and framed "
+                      "calls honour it; assign, windowed and datagram calls need every = 0");
+}
+
 int cs_check_range(const noise_gpu_cs *cs, uint64_t first, uint64_t count) {
   if (first + count < first) return api_arg_fail("first + count overflows");
   if (!cs) return api_arg_fail("null table");
@@ -246,10 +254,10 @@ int cs_records(bool decrypt, noise_gpu_cs *cs, noise_gpu_record *d_recs, uint64_
   const int rc = cs_check_records(cs, decrypt, d_recs, nrec, d_in, d_out, d_status);
   if (rc || nrec == 0) return rc;
   const hipStream_t st = (hipStream_t)stream;
-  API_TRY(cs_scratch(cs, cs_scratch_layout(false, true, nrec).total, st));
+  API_TRY(cs_scratch(cs, cs_inorder_scratch_bytes(cs->t, true, nrec), st));
   return cs_done(cs_inorder_call(
       decrypt, cs->t, cs_columns(d_recs), nrec, cs->scratch, d_status, st, [&](const CsColumns &mine) {
-        return launch_aead_records(decrypt, cs->t.keys, cs->t.nsess, mine.recs, nrec, d_in, d_out, d_ad,
+        return launch_aead_records(decrypt, mine.keys, mine.nkeys, mine.recs, nrec, d_in, d_out, d_ad,
                                    decrypt ? d_status : nullptr, st, len_sum);
       }));
 }
@@ -261,10 +269,10 @@ int cs_sessions(bool decrypt, noise_gpu_cs *cs, const uint32_t *d_sess, const ui
                                    len, d_status, nrec);
   if (rc || nrec == 0) return rc;
   const hipStream_t st = (hipStream_t)stream;
-  API_TRY(cs_scratch(cs, cs_scratch_layout(false, false, nrec).total, st));
+  API_TRY(cs_scratch(cs, cs_inorder_scratch_bytes(cs->t, false, nrec), st));
   return cs_done(cs_inorder_call(
       decrypt, cs->t, cs_columns(d_sess, nullptr), nrec, cs->scratch, d_status, st, [&](const CsColumns &mine) {
-        return launch_aead_sessions(decrypt, cs->t.keys, cs->t.nsess, reinterpret_cast<const uint32_t *>(mine.sess),
+        return launch_aead_sessions(decrypt, mine.keys, mine.nkeys, reinterpret_cast<const uint32_t *>(mine.sess),
                                     reinterpret_cast<const uint64_t *>(mine.nonce), d_in, in_stride, d_out,
                                     out_stride, len, decrypt ? d_status : nullptr, nrec, st);
       }));
@@ -342,11 +350,24 @@ int noise_gpu_cs_rekey(noise_gpu_cs *cs, const uint32_t *d_sess, uint64_t count,
   return NOISE_GPU_OK;
 }
 
+int noise_gpu_csrekey_set(noise_gpu_cs *cs, uint64_t every) {
+  if (!cs) return api_arg_fail("null table");
+  cs->t.every = every;
+  return NOISE_GPU_OK;
+}
+
+int noise_gpu_csrekey_get(const noise_gpu_cs *cs, uint64_t *every) {
+  if (!every) return api_arg_fail("null output");
+  if (!cs) return api_arg_fail("null table");
+  *every = cs->t.every;
+  return NOISE_GPU_OK;
+}
+
 int noise_gpu_cs_assign(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t sess_stride,
                         uint8_t *d_nonce, uint64_t nonce_stride, uint8_t *d_status, uint64_t nrec,
                         void *stream) {
   int rc = cs_check_assign(cs, d_sess, sess_stride, d_nonce, nonce_stride, nrec);
-  if (rc || nrec == 0) return rc;
+  if (rc || (rc = cs_check_unscheduled(cs)) || nrec == 0) return rc;
   if ((rc = api_check_device())) return rc;
   const hipStream_t st = (hipStream_t)stream;
   API_TRY(cs_scratch(cs, cs_assign_scratch_bytes(nrec), st));
@@ -381,7 +402,7 @@ int noise_gpu_cs_decrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess, cons
 
 int noise_gpu_cswin_reset(noise_gpu_cs *cs, uint64_t first, uint64_t count, void *stream) {
   int rc = cs_check_range(cs, first, count);
-  if (rc || count == 0) return rc;
+  if (rc || (rc = cs_check_unscheduled(cs)) || count == 0) return rc;
   if ((rc = api_check_device())) return rc;
   const hipStream_t st = (hipStream_t)stream;
   const bool fresh = !cs->w.next;
@@ -394,7 +415,7 @@ int noise_gpu_cswin_get(const noise_gpu_cs *cs, uint64_t first, uint64_t count, 
                         uint8_t *d_bits, void *stream) {
   if (reinterpret_cast<uintptr_t>(d_next) & 7u) return api_arg_fail("next array must be 8-byte aligned");
   int rc = cs_check_range(cs, first, count);
-  if (rc || count == 0) return rc;
+  if (rc || (rc = cs_check_unscheduled(cs)) || count == 0) return rc;
   if ((rc = api_check_device())) return rc;
   const hipStream_t st = (hipStream_t)stream;
   if (!cs->w.next) {  // never used a window: the fresh state
@@ -414,7 +435,7 @@ int noise_gpu_cswin_filter(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t ses
                            const uint8_t *d_nonce, uint64_t nonce_stride, uint8_t *d_status,
                            uint64_t nrec, void *stream) {
   int rc = cs_check_assign(cs, d_sess, sess_stride, d_nonce, nonce_stride, nrec);
-  if (rc || nrec == 0) return rc;
+  if (rc || (rc = cs_check_unscheduled(cs)) || nrec == 0) return rc;
   if (!d_status) return api_arg_fail("null status buffer");
   if ((rc = api_check_device())) return rc;
   const hipStream_t st = (hipStream_t)stream;
@@ -428,7 +449,7 @@ int noise_gpu_cswin_commit(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t ses
                            const uint8_t *d_nonce, uint64_t nonce_stride, uint8_t *d_status,
                            uint64_t nrec, void *stream) {
   int rc = cs_check_assign(cs, d_sess, sess_stride, d_nonce, nonce_stride, nrec);
-  if (rc || nrec == 0) return rc;
+  if (rc || (rc = cs_check_unscheduled(cs)) || nrec == 0) return rc;
   if (!d_status) return api_arg_fail("null status buffer");
   if ((rc = api_check_device())) return rc;
   const hipStream_t st = (hipStream_t)stream;
@@ -442,8 +463,8 @@ int noise_gpu_cswin_commit(noise_gpu_cs *cs, const uint8_t *d_sess, uint64_t ses
 int noise_gpu_cswin_decrypt_records(noise_gpu_cs *cs, const noise_gpu_record *d_recs, uint64_t nrec,
                                     const uint8_t *d_in, uint8_t *d_out, const uint8_t *d_ad,
                                     uint8_t *d_status, uint64_t len_sum, void *stream) {
-  const int rc = cs_check_records(cs, true, d_recs, nrec, d_in, d_out, d_status);
-  if (rc || nrec == 0) return rc;
+  int rc = cs_check_records(cs, true, d_recs, nrec, d_in, d_out, d_status);
+  if (rc || (rc = cs_check_unscheduled(cs)) || nrec == 0) return rc;
   const hipStream_t st = (hipStream_t)stream;
   API_TRY(cs_window_rows(cs, st));
   API_TRY(cs_scratch(cs, cs_scratch_layout(true, true, nrec).total, st));
@@ -458,9 +479,9 @@ int noise_gpu_cswin_decrypt_sessions(noise_gpu_cs *cs, const uint32_t *d_sess,
                                      const uint64_t *d_nonces, const uint8_t *d_in,
                                      uint64_t in_stride, uint8_t *d_out, uint64_t out_stride,
                                      uint32_t len, uint8_t *d_status, uint64_t nrec, void *stream) {
-  const int rc = cs_check_sessions(cs, true, true, d_sess, d_nonces, d_in, in_stride, d_out, out_stride, len,
-                                   d_status, nrec);
-  if (rc || nrec == 0) return rc;
+  int rc = cs_check_sessions(cs, true, true, d_sess, d_nonces, d_in, in_stride, d_out, out_stride, len,
+                             d_status, nrec);
+  if (rc || (rc = cs_check_unscheduled(cs)) || nrec == 0) return rc;
   const hipStream_t st = (hipStream_t)stream;
   API_TRY(cs_window_rows(cs, st));
   API_TRY(cs_scratch(cs, cs_scratch_layout(true, false, nrec).total, st));
@@ -476,8 +497,8 @@ int noise_gpu_dgram_seal(noise_gpu_cs *cs, uint32_t type, const uint32_t *d_sess
                          const noise_gpu_span *payload, const noise_gpu_span *pkt, noise_gpu_record *d_recs,
                          uint32_t *d_pkt_len, uint8_t *d_status, uint64_t len_sum, uint64_t nrec,
                          void *stream) {
-  const int rc = dg_check(cs, true, d_sess, d_peer, payload, pkt, d_recs, d_pkt_len, d_status, nrec);
-  if (rc || nrec == 0) return rc;
+  int rc = dg_check(cs, true, d_sess, d_peer, payload, pkt, d_recs, d_pkt_len, d_status, nrec);
+  if (rc || (rc = cs_check_unscheduled(cs)) || nrec == 0) return rc;
   const hipStream_t st = (hipStream_t)stream;
   API_TRY(cs_scratch(cs, cs_scratch_layout(false, true, nrec).total, st));
   return cs_done(dgram_seal_call(
@@ -491,8 +512,8 @@ int noise_gpu_dgram_seal(noise_gpu_cs *cs, uint32_t type, const uint32_t *d_sess
 int noise_gpu_dgram_open(noise_gpu_cs *cs, uint32_t type, const noise_gpu_span *pkt,
                          const noise_gpu_span *payload, noise_gpu_record *d_recs, uint32_t *d_payload_len,
                          uint8_t *d_status, uint64_t len_sum, uint64_t nrec, void *stream) {
-  const int rc = dg_check(cs, false, nullptr, nullptr, pkt, payload, d_recs, d_payload_len, d_status, nrec);
-  if (rc || nrec == 0) return rc;
+  int rc = dg_check(cs, false, nullptr, nullptr, pkt, payload, d_recs, d_payload_len, d_status, nrec);
+  if (rc || (rc = cs_check_unscheduled(cs)) || nrec == 0) return rc;
   const hipStream_t st = (hipStream_t)stream;
   API_TRY(cs_window_rows(cs, st));
   API_TRY(cs_scratch(cs, cs_scratch_layout(true, true, nrec).total, st));
@@ -513,13 +534,13 @@ int noise_gpu_framed_open(noise_gpu_cs *cs, const uint32_t *d_sess, const noise_
                           d_first_bad, d_consumed, d_plain_len, false, d_conn_status, d_total, nconn);
   if (rc || nconn == 0) return rc;
   const hipStream_t st = (hipStream_t)stream;
-  API_TRY(cs_scratch(cs, framed_scratch_layout(nconn, max_rec).total, st));
+  API_TRY(cs_scratch(cs, framed_scratch_layout(nconn, max_rec, cs->t.every != 0).total, st));
   const FramedOut out{d_first, d_nframes, d_first_bad, d_consumed, d_plain_len, d_conn_status, d_total};
   uint8_t *d_out = plain ? plain->base : wire->base;
   return cs_done(framed_open_call(
       cs->t, d_sess, *wire, plain, d_recs, d_status, max_rec, out, nconn, cs->scratch, st,
       [&](const CsColumns &mine) {
-        return launch_aead_records(true, cs->t.keys, cs->t.nsess, mine.recs, max_rec, wire->base, d_out, nullptr,
+        return launch_aead_records(true, mine.keys, mine.nkeys, mine.recs, max_rec, wire->base, d_out, nullptr,
                                    d_status, st, len_sum);
       }));
 }
@@ -533,12 +554,12 @@ int noise_gpu_framed_seal(noise_gpu_cs *cs, const uint32_t *d_sess, const noise_
                           nullptr, d_msg_used, d_wire_len, true, d_conn_status, d_total, nconn);
   if (rc || nconn == 0) return rc;
   const hipStream_t st = (hipStream_t)stream;
-  API_TRY(cs_scratch(cs, framed_scratch_layout(nconn, max_rec).total, st));
+  API_TRY(cs_scratch(cs, framed_scratch_layout(nconn, max_rec, cs->t.every != 0).total, st));
   const FramedOut out{d_first, d_nframes, nullptr, d_msg_used, d_wire_len, d_conn_status, d_total};
   return cs_done(framed_seal_call(
       cs->t, d_sess, *msg, *wire, max_payload, d_recs, d_status, max_rec, out, nconn, cs->scratch, st,
       [&](const CsColumns &mine) {
-        return launch_aead_records(false, cs->t.keys, cs->t.nsess, mine.recs, max_rec, msg->base, wire->base,
+        return launch_aead_records(false, mine.keys, mine.nkeys, mine.recs, max_rec, msg->base, wire->base,
                                    nullptr, nullptr, st, len_sum);
       }));
 }

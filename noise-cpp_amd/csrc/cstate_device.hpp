@@ -37,6 +37,31 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane) {
   return v;
 }
 
+// ---- the in-band rekey schedule (noise_gpu_csrekey_*): "REKEY when the
+// counter, after it moved, is a multiple of `every`" as arithmetic on ranks.
+// A session enters a batch with counter n0; its record of rank r carries nonce
+// n0 + r, and the move behind rank j - 1 leaves the counter at (n0 + j) mod
+// 2^64.  The one definition the kernels, the emulation driver's model and the
+// CPU unit test share.
+//
+// cs_rekey_first: the smallest j >= 1 with (n0 + j) mod 2^64 a multiple of
+// every, in 1 .. every.  Only n0 = 2^64-1 can wrap (2^64-2 has no room), and
+// it wraps to 0, a multiple of every `every`.
+__host__ __device__ inline uint64_t cs_rekey_first(uint64_t n0, uint64_t every) {
+  return n0 == ~0ull ? 1ull : every - n0 % every;
+}
+// the boundaries among j = 1 .. c: the REKEYs behind a session's first c
+// accepted records, and so the generation the record of rank c runs under
+__host__ __device__ inline uint64_t cs_rekey_gens(uint64_t n0, uint64_t c, uint64_t every) {
+  const uint64_t first = cs_rekey_first(n0, every);
+  return c < first ? 0ull : (c - first) / every + 1ull;
+}
+// the rank of the record that opens generation g >= 1 (g <= cs_rekey_gens of
+// the accepted count, so nothing here overflows); rank 0 opens generation 0
+__host__ __device__ inline uint64_t cs_rekey_opener(uint64_t n0, uint64_t g, uint64_t every) {
+  return g == 0 ? 0ull : cs_rekey_first(n0, every) + (g - 1ull) * every;
+}
+
 __device__ __forceinline__ uint32_t cs_sess_at(const uint8_t *sess, uint64_t stride, uint64_t i) {
   return *reinterpret_cast<const uint32_t *>(sess + i * stride);
 }

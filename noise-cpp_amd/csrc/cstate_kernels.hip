@@ -115,8 +115,8 @@ struct CsOut {
   uint8_t *status;  // or null
 };
 
-// record i of a keyed session with counter n0, rank r
-__device__ __forceinline__ void cs_apply_one(const CsOut &o, uint64_t i, bool keyless, uint64_t n0,
+// record i of a keyed session with counter n0, rank r; true: accepted (a nonce was assigned)
+__device__ __forceinline__ bool cs_apply_one(const CsOut &o, uint64_t i, bool keyless, uint64_t n0,
                                              uint32_t r) {
   uint32_t st;
   if (keyless) {
@@ -131,6 +131,7 @@ __device__ __forceinline__ void cs_apply_one(const CsOut &o, uint64_t i, bool ke
     st = NOISE_GPU_REC_NONCE;
   }
   if (o.status) o.status[i] = (uint8_t)st;
+  return st == NOISE_GPU_REC_OK;
 }
 
 // counter after c records of a keyed session
@@ -376,6 +377,26 @@ __global__ __launch_bounds__(64) void k_cs_set(uint8_t *keys, uint64_t *ctr, uin
   }
 }
 
+// a key row as words; true: all zero (keyless)
+__device__ __forceinline__ bool cs_load_row(const uint4 *kp, uint32_t k[8]) {
+  const uint4 a = kp[0], b = kp[1];
+  k[0] = a.x; k[1] = a.y; k[2] = a.z; k[3] = a.w;
+  k[4] = b.x; k[5] = b.y; k[6] = b.z; k[7] = b.w;
+  return (a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w) == 0u;
+}
+__device__ __forceinline__ void cs_store_row(uint4 *kp, const uint32_t k[8]) {
+  kp[0] = make_uint4(k[0], k[1], k[2], k[3]);
+  kp[1] = make_uint4(k[4], k[5], k[6], k[7]);
+}
+// k <- REKEY(k): the first 32 bytes of the keystream block 1 under nonce 2^64-2
+__device__ __forceinline__ void cs_rekey_words(uint32_t k[8]) {
+  const uint64_t n = ~0ull - 1ull;
+  uint32_t ks[16];
+  chacha20_block(k, 1u, (uint32_t)n, (uint32_t)(n >> 32), ks);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) k[i] = ks[i];
+}
+
 // REKEY (noise.cpp:429-439): k <- ENCRYPT(k, 2^64-2, empty, 0^32)[0..32); a
 // keyless row stays keyless, an index >= nsess is skipped
 __global__ __launch_bounds__(64) void k_cs_rekey(uint8_t *keys, uint32_t nsess, const uint32_t *sess,
@@ -386,13 +407,163 @@ __global__ __launch_bounds__(64) void k_cs_rekey(uint8_t *keys, uint32_t nsess, 
     uint4 *kp = reinterpret_cast<uint4 *>(keys + 32ull * s);
     const uint4 ka = kp[0], kb = kp[1];
     if ((ka.x | ka.y | ka.z | ka.w | kb.x | kb.y | kb.z | kb.w) == 0u) continue;
-    const uint32_t k[8] = {ka.x, ka.y, ka.z, ka.w, kb.x, kb.y, kb.z, kb.w};
-    const uint64_t n = ~0ull - 1ull;
-    uint32_t ks[16];
-    chacha20_block(k, 1u, (uint32_t)n, (uint32_t)(n >> 32), ks);
-    kp[0] = make_uint4(ks[0], ks[1], ks[2], ks[3]);
-    kp[1] = make_uint4(ks[4], ks[5], ks[6], ks[7]);
+    uint32_t k[8] = {ka.x, ka.y, ka.z, ka.w, kb.x, kb.y, kb.z, kb.w};
+    cs_rekey_words(k);
+    cs_store_row(kp, k);
   }
+}
+
+// ---- the in-band rekey schedule (t.every != 0) -------------------------------------
+// "REKEY when the counter, after it moved, is a multiple of every" (the loop
+// of include/noise_gpu.h; the arithmetic is cstate_device.hpp's cs_rekey_*).
+// The AEAD kernels take one key table and an index per record, so a scheduled
+// call gives them a private table `rows` of nrec rows, indexed by sorted
+// position: the head of session s's run (start[s]) holds a copy of the table's
+// row, and the record that opens generation g >= 1 -- rank r_g, the only one of
+// the generation whose nonce is a multiple of every -- holds REKEY^g at
+// start[s] + r_g.  Every accepted record's private index becomes the row of
+// its generation's opener.
+//   mark   (k_csr_mark) every private index starts as kCsRefused, so that one
+//          the sort drops (>= nsess) cannot name a private row
+//   apply  (k_csr_apply) k_cs_apply, and the private index of every accepted
+//          record and of every record of a keyless session (its head row, zero)
+//   chain  (k_csr_chain) the run's last lane, before k_cs_tails moves n: the
+//          head row, then one chacha20_block per boundary the accepted records
+//          cross, serially; the rows of the openers, and the last one back into
+//          the table -- also when the last accepted record hits the boundary and
+//          no record of the batch uses the new key
+// A batch of at most one wave: k_csr_small, where a row's index is the lane of
+// the record that opens the generation.
+
+// every private index, before the assignment: refused
+__global__ __launch_bounds__(64) void k_csr_mark(uint8_t *kill, uint64_t kill_stride, uint64_t nrec) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 64 + threadIdx.x; i < nrec; i += (uint64_t)gridDim.x * 64)
+    *reinterpret_cast<uint32_t *>(kill + i * kill_stride) = kCsRefused;
+}
+
+// the rank, within its session, of the record whose row an accepted record of
+// rank r reads: the opener of r's generation
+__device__ __forceinline__ uint64_t csr_row_rank(uint64_t n0, uint32_t r, uint64_t every) {
+  return cs_rekey_opener(n0, cs_rekey_gens(n0, r, every), every);
+}
+
+__global__ __launch_bounds__(64) void k_csr_apply(const unsigned long long *pair, const uint32_t *hdr,
+                                                  const uint32_t *start, const uint8_t *keys,
+                                                  const uint64_t *ctr, uint64_t every, CsOut o) {
+  const uint32_t n = hdr[0];
+  for (uint64_t p = (uint64_t)blockIdx.x * 64 + threadIdx.x; p < n; p += (uint64_t)gridDim.x * 64) {
+    const unsigned long long pr = pair[p];
+    const uint32_t s = (uint32_t)pr, i = (uint32_t)(pr >> 32), head = start[s], r = (uint32_t)p - head;
+    const bool keyless = key_row_zero(keys, s);
+    const uint64_t n0 = ctr[s];
+    const bool accepted = cs_apply_one(o, i, keyless, n0, r);
+    uint32_t row;
+    if (keyless)
+      row = head;
+    else if (accepted)
+      row = head + (uint32_t)csr_row_rank(n0, r, every);
+    else
+      continue;  // refused: the mark stays
+    *reinterpret_cast<uint32_t *>(o.kill + (uint64_t)i * o.kill_stride) = row;
+  }
+}
+
+// the generations of a keyed session with counter n0 and `acc` accepted
+// records, from its row k: put(rank, k) for every opener of rank < acc; k ends
+// as the row the table keeps
+template <class Put>
+__device__ __forceinline__ void csr_walk(uint32_t k[8], uint64_t n0, uint64_t acc, uint64_t every, Put put) {
+  const uint64_t gens = cs_rekey_gens(n0, acc, every);
+  uint64_t r = cs_rekey_opener(n0, 1, every);
+#pragma unroll 1
+  for (uint64_t g = 0; g < gens; ++g, r += every) {
+    cs_rekey_words(k);
+    if (r < acc) put(r, k);
+  }
+}
+
+__global__ __launch_bounds__(64) void k_csr_chain(const unsigned long long *pair, const uint32_t *hdr,
+                                                  const uint32_t *start, uint8_t *keys,
+                                                  const uint64_t *ctr, uint64_t every, uint8_t *rows) {
+  const uint32_t n = hdr[0];
+  for (uint64_t p = (uint64_t)blockIdx.x * 64 + threadIdx.x; p < n; p += (uint64_t)gridDim.x * 64) {
+    const uint32_t s = (uint32_t)pair[p];
+    if (p + 1 < n && (uint32_t)pair[p + 1] == s) continue;
+    const uint32_t head = start[s];
+    uint4 *kp = reinterpret_cast<uint4 *>(keys + 32ull * s);
+    uint32_t k[8];
+    const bool keyless = cs_load_row(kp, k);
+    cs_store_row(reinterpret_cast<uint4 *>(rows + 32ull * head), k);
+    if (keyless) continue;
+    const uint64_t n0 = ctr[s], room = 0xfffffffffffffffeull - n0, count = (uint64_t)((uint32_t)p - head) + 1u;
+    csr_walk(k, n0, count < room ? count : room, every, [&](uint64_t r, const uint32_t *kg) {
+      cs_store_row(reinterpret_cast<uint4 *>(rows + 32ull * (head + r)), kg);
+    });
+    cs_store_row(kp, k);
+  }
+}
+
+// the lane of the n-th (from 0) set bit of m
+__device__ __forceinline__ uint32_t csr_nth_lane(uint64_t m, uint64_t n) {
+#pragma unroll 1
+  for (; n; --n) m &= m - 1;
+  return (uint32_t)__builtin_ctzll(m);
+}
+
+// k_cs_small under the schedule: a session's rows sit at the lanes of its
+// openers, and its last lane walks the chain and moves both row and counter
+__global__ __launch_bounds__(64) void k_csr_small(const uint8_t *sess, uint64_t sess_stride, uint8_t *keys,
+                                                  uint64_t *ctr, uint32_t nsess, int bits, uint32_t nrec,
+                                                  uint64_t every, uint8_t *rows, CsOut o) {
+  const uint32_t lane = threadIdx.x;
+  const bool have = lane < nrec;
+  const uint32_t s = have ? cs_sess_at(sess, sess_stride, lane) : 0u;
+  const bool valid = have && s < nsess;
+  const uint64_t peers = cs_match(s, bits, valid);
+  uint64_t n0 = 0;
+  bool keyless = true;
+  if (valid) {
+    n0 = ctr[s];
+    keyless = key_row_zero(keys, s);
+  }
+  __syncthreads();  // every lane has read n[s] and k[s] before a tail lane moves them
+  uint32_t *mine = have ? reinterpret_cast<uint32_t *>(o.kill + (uint64_t)lane * o.kill_stride) : nullptr;
+  if (valid) {
+    const uint32_t r = cs_below(peers), head = (uint32_t)__builtin_ctzll(peers);
+    const uint64_t room = 0xfffffffffffffffeull - n0, count = (uint64_t)__builtin_popcountll(peers);
+    const bool accepted = cs_apply_one(o, lane, keyless, n0, r);  // a refused record: the mark
+    if (keyless)
+      *mine = head;
+    else if (accepted)
+      *mine = csr_nth_lane(peers, csr_row_rank(n0, r, every));
+    if ((peers >> lane) >> 1 == 0) {  // the tail
+      uint4 *kp = reinterpret_cast<uint4 *>(keys + 32ull * s);
+      uint32_t k[8];
+      cs_load_row(kp, k);
+      cs_store_row(reinterpret_cast<uint4 *>(rows + 32ull * head), k);
+      if (!keyless) {
+        csr_walk(k, n0, count < room ? count : room, every, [&](uint64_t rr, const uint32_t *kg) {
+          cs_store_row(reinterpret_cast<uint4 *>(rows + 32ull * csr_nth_lane(peers, rr)), kg);
+        });
+        cs_store_row(kp, k);
+        ctr[s] = cs_advance(n0, (uint32_t)count);
+      }
+    }
+  } else if (have) {
+    *mine = kCsRefused;
+    if (o.status) o.status[lane] = (uint8_t)NOISE_GPU_REC_BAD_KEY;
+  }
+}
+
+// after the AEAD kernels of a scheduled decrypt: a record of a session
+// (< nsess) whose private index is the mark was refused, and reads BAD_KEY
+// from them; one that names no session keeps that BAD_KEY
+__global__ __launch_bounds__(64) void k_csr_fix(const uint8_t *sess, uint64_t sess_stride,
+                                                const uint8_t *kill, uint64_t kill_stride, uint32_t nsess,
+                                                uint8_t *status, uint64_t nrec) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 64 + threadIdx.x; i < nrec; i += (uint64_t)gridDim.x * 64)
+    if (cs_sess_at(kill, kill_stride, i) == kCsRefused && cs_sess_at(sess, sess_stride, i) < nsess)
+      status[i] = (uint8_t)NOISE_GPU_REC_NONCE;
 }
 
 // ---- launchers ---------------------------------------------------------------------
@@ -479,6 +650,46 @@ hipError_t launch_cs_fix(const uint8_t *sess, uint64_t sess_stride, const uint8_
   if (nrec == 0) return hipSuccess;
   hipLaunchKernelGGL(k_cs_fix, dim3(cs_capped((nrec + 63) / 64)), dim3(64), 0, stream, sess,
                      sess_stride, kill, kill_stride, status, nrec);
+  return hipGetLastError();
+}
+
+hipError_t launch_csr_assign(const CsTableView &t, const CsAssign &a, uint8_t *rows, void *scratch,
+                             hipStream_t stream) {
+  if (a.nrec == 0) return hipSuccess;
+  if (t.every == 0 || !a.kill || !rows) return hipErrorInvalidValue;
+  const dim3 b64(64);
+  const CsOut o{a.nonce, a.nonce_stride, a.nonce2, a.nonce2_stride, a.kill, a.kill_stride, a.status};
+  if (a.nrec <= 64) {
+    int bits = 0;
+    for (uint32_t v = t.nsess - 1u; v; v >>= 1) ++bits;
+    hipLaunchKernelGGL(k_csr_small, dim3(1), b64, 0, stream, a.sess, a.sess_stride, t.keys, t.ctr, t.nsess,
+                       bits, (uint32_t)a.nrec, t.every, rows, o);
+    return hipGetLastError();
+  }
+  const dim3 gr(cs_capped((a.nrec + 63) / 64));
+  hipLaunchKernelGGL(k_csr_mark, gr, b64, 0, stream, a.kill, a.kill_stride, a.nrec);
+  CsSorted sorted;
+  const hipError_t e =
+      launch_cs_sort(a.sess, a.sess_stride, t.nsess, a.nrec, scratch, a.status, stream, &sorted);
+  if (e != hipSuccess) return e;
+  const unsigned long long *pair = sorted.pair;
+  const uint32_t *hdr = sorted.hdr;
+  hipLaunchKernelGGL(k_cs_heads, gr, b64, 0, stream, pair, hdr, t.start);
+  hipLaunchKernelGGL(k_csr_apply, gr, b64, 0, stream, pair, hdr, (const uint32_t *)t.start,
+                     (const uint8_t *)t.keys, (const uint64_t *)t.ctr, t.every, o);
+  hipLaunchKernelGGL(k_csr_chain, gr, b64, 0, stream, pair, hdr, (const uint32_t *)t.start, t.keys,
+                     (const uint64_t *)t.ctr, t.every, rows);
+  hipLaunchKernelGGL(k_cs_tails, gr, b64, 0, stream, pair, hdr, (const uint32_t *)t.start,
+                     (const uint8_t *)t.keys, t.ctr);
+  return hipGetLastError();
+}
+
+hipError_t launch_csr_fix(const uint8_t *sess, uint64_t sess_stride, const uint8_t *kill,
+                          uint64_t kill_stride, uint32_t nsess, uint8_t *status, uint64_t nrec,
+                          hipStream_t stream) {
+  if (nrec == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_csr_fix, dim3(cs_capped((nrec + 63) / 64)), dim3(64), 0, stream, sess, sess_stride,
+                     kill, kill_stride, nsess, status, nrec);
   return hipGetLastError();
 }
 

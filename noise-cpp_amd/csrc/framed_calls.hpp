@@ -11,16 +11,18 @@ namespace noise_amd {
 
 // One call's scratch, as offsets from a 16-byte aligned base: the framing's own
 // columns (launchers.hpp, FramedColumns), each rounded up to 16, in front of
-// the table call's cs_scratch_layout(false, true, max_rec) at `table`.
+// the table call's scratch at `table`: cs_scratch_layout(false, true, max_rec),
+// or with rekey (a table with a schedule) cs_rekey_scratch_layout(true, max_rec).
 struct FramedScratchLayout {
   size_t count, first, part, table, total;
 };
-inline FramedScratchLayout framed_scratch_layout(uint64_t nconn, uint64_t max_rec) {
+inline FramedScratchLayout framed_scratch_layout(uint64_t nconn, uint64_t max_rec, bool rekey = false) {
   FramedScratchLayout l{};
   l.first = l.count + align16(4 * nconn);
   l.part = l.first + align16(4 * nconn);
   l.table = l.part + align16(8 * (framed_tiles(nconn) + 1));
-  l.total = l.table + cs_scratch_layout(false, true, max_rec).total;
+  l.total = l.table + (rekey ? cs_rekey_scratch_layout(true, max_rec).total
+                             : cs_scratch_layout(false, true, max_rec).total);
   return l;
 }
 inline FramedColumns framed_columns(const FramedScratchLayout &l, uint8_t *scratch) {
@@ -30,13 +32,13 @@ inline FramedColumns framed_columns(const FramedScratchLayout &l, uint8_t *scrat
 
 // aead(mine): the decrypt launch on the private descriptors mine.recs, in =
 // wire.base, out = plain ? plain->base : wire.base, reporting into `status`.
-// scratch: framed_scratch_layout(nconn, max_rec).total bytes.
+// scratch: framed_scratch_layout(nconn, max_rec, t.every != 0).total bytes.
 template <class Aead>
 hipError_t framed_open_call(const CsTableView &t, const uint32_t *sess, const noise_gpu_span &wire,
                             const noise_gpu_span *plain, noise_gpu_record *recs, uint8_t *status,
                             uint64_t max_rec, const FramedOut &out, uint64_t nconn, uint8_t *scratch,
                             hipStream_t st, Aead aead) {
-  const FramedScratchLayout l = framed_scratch_layout(nconn, max_rec);
+  const FramedScratchLayout l = framed_scratch_layout(nconn, max_rec, t.every != 0);
   const FramedColumns c = framed_columns(l, scratch);
   hipError_t e = launch_framed_count(true, wire, 0, c, nconn, st);
   if (e != hipSuccess) return e;
@@ -49,13 +51,13 @@ hipError_t framed_open_call(const CsTableView &t, const uint32_t *sess, const no
 
 // aead(mine): the encrypt launch on the private descriptors mine.recs, in =
 // msg.base, out = wire.base.
-// scratch: framed_scratch_layout(nconn, max_rec).total bytes.
+// scratch: framed_scratch_layout(nconn, max_rec, t.every != 0).total bytes.
 template <class Aead>
 hipError_t framed_seal_call(const CsTableView &t, const uint32_t *sess, const noise_gpu_span &msg,
                             const noise_gpu_span &wire, uint32_t max_payload, noise_gpu_record *recs,
                             uint8_t *status, uint64_t max_rec, const FramedOut &out, uint64_t nconn,
                             uint8_t *scratch, hipStream_t st, Aead aead) {
-  const FramedScratchLayout l = framed_scratch_layout(nconn, max_rec);
+  const FramedScratchLayout l = framed_scratch_layout(nconn, max_rec, t.every != 0);
   const FramedColumns c = framed_columns(l, scratch);
   hipError_t e = launch_framed_count(false, msg, max_payload, c, nconn, st);
   if (e != hipSuccess) return e;

@@ -200,6 +200,7 @@ struct CsTableView {
   uint64_t *ctr;    // [nsess] the counters n
   uint32_t *start;  // [nsess] rank scratch: where a session's run starts in the sorted batch
   uint32_t nsess;
+  uint64_t every = 0;  // the in-band rekey schedule (noise_gpu_csrekey_set); 0: off
 };
 // One batch: record i belongs to session *(uint32_t *)(sess + i * sess_stride).
 // An accepted record's nonce goes to nonce + i * nonce_stride (and to nonce2,
@@ -242,6 +243,22 @@ hipError_t launch_cs_set(const CsTableView &t, uint64_t first, uint64_t count, c
 // REKEY of sess[0..count), or of sessions [0, count) when sess is null
 hipError_t launch_cs_rekey(const CsTableView &t, const uint32_t *sess, uint64_t count,
                            hipStream_t stream);
+// launch_cs_assign under the schedule t.every != 0 (cstate_device.hpp,
+// cs_rekey_*): besides the nonces, statuses and counters, every touched keyed
+// session's row moves on by the REKEYs its accepted records cross, and the
+// uint32 at a.kill (required) + i * a.kill_stride becomes record i's row in
+// `rows`, a private [a.nrec][32] key table (16-byte aligned) for the AEAD
+// kernels: an accepted record's row holds the key of its generation, a keyless
+// session's a copy of its all-zero row, and a refused record or one whose
+// session is >= nsess gets 0xffffffff.  Rows no record names are not written.
+// scratch: as launch_cs_assign.
+hipError_t launch_csr_assign(const CsTableView &t, const CsAssign &a, uint8_t *rows, void *scratch,
+                             hipStream_t stream);
+// after the AEAD kernels of a scheduled decrypt: status[i] = NOISE_GPU_REC_NONCE
+// where the private index is 0xffffffff and the caller's names a session
+hipError_t launch_csr_fix(const uint8_t *sess, uint64_t sess_stride, const uint8_t *kill,
+                          uint64_t kill_stride, uint32_t nsess, uint8_t *status, uint64_t nrec,
+                          hipStream_t stream);
 
 // ---- replay windows of a CipherState table (cswin_kernels.hip) -----------
 struct CsWindowView {

@@ -59,6 +59,20 @@ class DeviceCipherStates {
   void rekey(const std::uint32_t *d_sess = nullptr, std::uint64_t count = 0, void *stream = nullptr) {
     check(noise_gpu_cs_rekey(cs_, d_sess, count, stream), "noise_gpu_cs_rekey");
   }
+  // The in-band schedule (noise_gpu_csrekey_*): every session does rekey()
+  // whenever its counter, after an accepted record moved it, is a multiple of
+  // `every` -- on the GPU, inside a batch.  0 = off.  Honoured by
+  // encrypt_records / decrypt_records / encrypt_sessions / decrypt_sessions /
+  // framed_seal / framed_open; assign, the windowed calls, seal and open throw
+  // invalid_argument on a scheduled table.
+  void set_rekey_every(std::uint64_t every) {
+    check(noise_gpu_csrekey_set(cs_, every), "noise_gpu_csrekey_set");
+  }
+  [[nodiscard]] std::uint64_t rekey_every() const {
+    std::uint64_t every = 0;
+    check(noise_gpu_csrekey_get(cs_, &every), "noise_gpu_csrekey_get");
+    return every;
+  }
 
   // A host CipherState continuing session s: same key, next nonce (like
   // transport::Batcher::state).  Synchronises `stream`.

@@ -174,6 +174,8 @@ def load(path=LIB_PATH):
                                                          vp]),
         "noise_gpu_cs_decrypt_sessions": (ctypes.c_int, [vp, u8p, u8p, u64, u8p, u64, u32, u8p, u64,
                                                          vp]),
+        "noise_gpu_csrekey_set": (ctypes.c_int, [vp, u64]),
+        "noise_gpu_csrekey_get": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint64)]),
         "noise_gpu_cswin_reset": (ctypes.c_int, [vp, u64, u64, vp]),
         "noise_gpu_cswin_get": (ctypes.c_int, [vp, u64, u64, u8p, u8p, vp]),
         "noise_gpu_cswin_filter": (ctypes.c_int, [vp, u8p, u64, u8p, u64, u8p, u64, vp]),
@@ -389,6 +391,18 @@ class CipherStateTable:
         """d_sess: int32 tensor of count session indices, or None: all."""
         _check(self.lib.noise_gpu_cs_rekey(self.h, _ptr(d_sess), count, _stream(stream)),
                "noise_gpu_cs_rekey")
+
+    # ---- the in-band rekey schedule (noise_gpu_csrekey_*): REKEY whenever a
+    # session's counter, after it moved, is a multiple of every
+    def set_rekey_every(self, every):
+        """0 = off.  The in-order and framed calls issued afterwards honour it;
+        assign, the windowed and the datagram calls refuse a scheduled table."""
+        _check(self.lib.noise_gpu_csrekey_set(self.h, every), "noise_gpu_csrekey_set")
+
+    def rekey_every(self):
+        every = ctypes.c_uint64(0)
+        _check(self.lib.noise_gpu_csrekey_get(self.h, ctypes.byref(every)), "noise_gpu_csrekey_get")
+        return every.value
 
     def assign(self, d_sess, d_nonce, nrec, d_status=None, sess_stride=4, nonce_stride=8,
                sess_offset=0, nonce_offset=0, stream=None):

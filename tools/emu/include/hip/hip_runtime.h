@@ -183,8 +183,11 @@ void run_grid(K kernel, dim3 g, dim3 b, size_t shmem, A... args) {
     for (auto &x : th) x.join();
   }
 }
+// kernel launches so far: a test can compare two paths launch for launch
+inline std::atomic<uint64_t> launches{0};
 template <class K, class... A>
 void launch_shm(K kernel, dim3 g, dim3 b, size_t shmem, A... args) {
+  ++launches;
   if (async_kernel && reinterpret_cast<void *>(kernel) == async_kernel) {
     ++async_running;
     std::lock_guard<std::mutex> lk(async_mu);
